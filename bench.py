@@ -17,6 +17,10 @@ Prints ONE JSON line (rank 0): metric/value/unit/... plus
   accuracy     — the metric's second half: GPU torques / forces against the CPU oracle on the same seeded sample;
   cpu_baseline — the CPU oracle (oracle/, "port", -O3 -march=native, OpenMP) timed on a bounded sample of the
                  same workload on this box's host cores (rank 0, N=1 only).
+A plain run does what the headline figure needs and no more: set-up, warm-up, the `--steps` timed steps, the line (with
+the roofline figures of those very steps).  `--full` adds everything measured in runs of its own: the secondary figures,
+the legs of the other BASELINE configurations, accuracy and cpu_baseline.  `--dump-outputs DIR` writes the results of the
+last timed step as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -102,6 +106,13 @@ def parse_args():
     ap.add_argument("--batch", type=int, default=4096, help="instances per GPU")
     ap.add_argument("--n-steps", type=int, default=16, help="MPC horizon")
     ap.add_argument("--gaits", type=str, default="trot")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the secondary figures, the legs of the other BASELINE "
+                         "configurations, the CPU baseline and the accuracy against the CPU oracle (each can be taken out again "
+                         "with its --no-* flag); without --full a run sets up, warms up, times --steps steps and prints its line")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the MPC result, the force command and "
+                         "every WBC output) as DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-collective", action="store_true", help="N > 1: skip the per-step all-gather of torques")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (profiling runs)")
@@ -182,8 +193,31 @@ class StubEngine:
         return dict(iters=np.full(self.B, 25, np.int32))
 
 
+DUMP_CAP_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, arrays, prefix=""):
+    """`--dump-outputs DIR`: what the caller of the timed path holds after the last timed step, one float64 `DIR/<name>.npy` per
+    array, whole wherever everything fits the 64 MB cap (the default shape: 17 MB).  Beyond it the arrays are taken smallest
+    first, and one that exceeds an equal share of what is left is cut down to a fixed, seeded sample of its instances (leading
+    dimension, ascending): the same sample in every run of the same shape."""
+    os.makedirs(path, exist_ok=True)
+    host = sorted(((name, np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float64)) for name, t in arrays.items()),
+                  key=lambda na: na[1].nbytes)
+    left = DUMP_CAP_BYTES
+    for i, (name, a) in enumerate(host):
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            rows = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(20260000).choice(a.shape[0], size=rows, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+
+
 def main():
     args = parse_args()
+    if not args.full:  # a plain run: the headline figure and nothing beside it
+        args.no_secondary = args.no_configs = args.no_cpu_baseline = True
     if args.dry_ranks > 0:
         raise SystemExit(dry_ranks(args))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -323,6 +357,11 @@ def main():
     if collective:
         gather_ok = pipe.check_last(rank, world, wbc_bufs[(W + K - 1) & 1]["tau_ff"])
         elapsed_nc = timed_region(W + K, K, False)
+    if args.dump_outputs:
+        # the last timed step's results as its caller holds them (every timed region ends synchronised); rank r > 0 of a
+        # multi-GPU run writes its own shard as rank<r>_<name>.npy
+        last = dict(wbc_bufs[(n_in - 1) & 1], mpc_out=mpc_out, f_cmd=f_cmd)
+        dump_outputs(args.dump_outputs, last, prefix=("rank%d_" % rank) if rank else "")
 
     total_steps = world * B * K
     value = total_steps / elapsed

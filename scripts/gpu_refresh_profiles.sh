@@ -41,5 +41,5 @@ echo "phases done"
 # the ONE bench line last, with this call's counter summary + stamp in place (bench.py quotes roofline.traffic from profiles/ only when
 # the stamp matches the kernel sources)
 cp $OUT/${ROUND}_pmc_summary_*.json $OUT/${ROUND}_pmc_stamp_*.json $R/profiles/
-python3 bench.py > $OUT/${ROUND}_bench_line.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/${ROUND}_bench_line.json 2> $OUT/bench.err
 echo "bench done"
