@@ -87,7 +87,7 @@ struct MpcArgs {
                       // batch that is resident all at once, mpc_preemptive_launch)
 };
 constexpr int kPreMaxLevels = 9;
-// pre_ctr words (one layout for the kernel, mpc_kernel.hip, and the host readers, qrw_api.hip): takers that took a solve, solves
+// pre_ctr words (one layout for the kernel, mpc_kernel.hip, and the host readers, qrw_api.hip and qrw_selftest.hip): takers that took a solve, solves
 // parked in total, finished instances, error (3, 4: a taker's solve, reserved for it, did not arrive; 2: a level's queue overran;
 // 9: forced by a test), progress (chunks ended: the give-up clock restarts on it), claims (taker workgroups spoken for: by a solve
 // parked for them, or by leaving empty-handed); head of level l at kPreLevelWord + 2 l, its tail at + 2 l + 1

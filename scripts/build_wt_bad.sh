@@ -9,7 +9,7 @@ for sha in "$@"; do
   ( cd $R/build/wt/$sha/quadruped-reactive-walking_amd/csrc && make -s >/dev/null 2>&1
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-result -Wno-unused-function -Wno-pass-failed \
       -mllvm -amdgpu-sched-strategy=max-ilp -DQRW_PROFILE_PHASES $QRW_EXTRA -c -o mpc_bad.o mpc_kernel.hip 2>/dev/null
-    hipcc --offload-arch=gfx950 -shared -fPIC -o ../libqrw_hip_bad.so qrw_api.o mpc_bad.o wbc_kernel.o planner_kernel.o controller_kernel.o )
+    hipcc --offload-arch=gfx950 -shared -fPIC -o ../libqrw_hip_bad.so $(ls *.o | grep -v -x mpc_kernel.o) )
   ( cd $R/build/wt/$sha/oracle && make -s libqrw_oracle.so >/dev/null )
   echo built $sha
 done

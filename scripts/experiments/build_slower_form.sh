@@ -18,7 +18,7 @@ cp $R/quadruped-reactive-walking_amd/csrc/*.h $R/quadruped-reactive-walking_amd/
 ln -sfn $R/include "$S/include"   # the sources include ../../include/...
 (cd "$S/pkg/csrc" && patch -p1 < $R/scripts/experiments/slower_forms.patch)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-result -Wno-unused-function -Wno-pass-failed"
-for f in qrw_api mpc_kernel wbc_kernel planner_kernel controller_kernel; do
+for f in qrw_api qrw_selftest mpc_kernel wbc_kernel planner_kernel controller_kernel; do
   extra=""
   if [ -n "$3" ]; then extra="-DQRW_PROFILE_PHASES"; elif [ $f = mpc_kernel ]; then extra="-mllvm -amdgpu-sched-strategy=max-ilp"; fi
   hipcc $FLAGS $extra $2 -c -o "$S/$f.o" "$S/pkg/csrc/$f.hip"

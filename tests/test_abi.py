@@ -40,6 +40,25 @@ def test_header_and_binding_agree(lib):
         assert hasattr(lib, name), name
 
 
+def test_every_handle_entry_point_refuses_a_null_handle(lib):
+    """Every entry point that takes a handle answers a null one (all other arguments zero / NULL) with -1 and an error text that
+    begins with its own name, before it touches a device.  qrw_destroy and qrw_state_bytes accept it: 0, error text untouched."""
+    import qrw_hip
+
+    no_handle = {"qrw_create", "qrw_last_error", "qrw_selftest_sweeps", "qrw_device_cu_count", "qrw_stream_create",
+                 "qrw_stream_destroy", "qrw_test_known_answer", "qrw_test_poison_probe"}
+    tolerant = {"qrw_destroy", "qrw_state_bytes"}
+    sigs = {**qrw_hip.SIGNATURES, **qrw_hip.TEST_SIGNATURES}
+    names = sorted(n for n in sigs if n not in no_handle and n not in tolerant)
+    assert len(names) > 30 and all(sigs[n][1][0] is qrw_hip._vp for n in names)
+    for name in names:
+        rc = getattr(lib, name)(*[t() for t in sigs[name][1]])
+        text = lib.qrw_last_error().decode()
+        assert rc == -1 and text.startswith(name + ":"), (name, rc, text)
+        for t in sorted(tolerant):
+            assert getattr(lib, t)(None) == 0 and lib.qrw_last_error().decode() == text, (t, name)
+
+
 def test_shipped_sources_hold_no_experiment_paths(tmp_path):
     """What lost its A/B is NOT in the translation units of libqrw_hip.so.  The timing experiments that compute wrong results on
     purpose (what a re-arrangement of the sweeps could gain at most) live in scripts/experiments/timing_experiments.patch, applied

@@ -331,7 +331,7 @@ def test_two_caller_threads_with_their_own_handles(synth_mod):
 def test_one_handle_per_visible_device_stepped_from_one_thread(synth_mod):
     """Multi-GPU readiness (the batch is sharded over the GPUs of a node, one shard per device): ONE
     process creates a handle on EVERY visible device and steps them from one thread while torch's current device stays 0 -- every
-    entry point has to switch to its handle's device and back (DeviceScope, qrw_api.hip), the known-answer gate runs per device,
+    entry point has to switch to its handle's device and back (DeviceScope, csrc/qrw_host.h), the known-answer gate runs per device,
     and tensors on another device than the handle's are refused.  Every device must return, bit for bit, what device 0 returns for
     the same shard (same kernels, same arithmetic).  Skips on a box with one GPU: the first multi-GPU box that runs the suite
     exercises it."""
