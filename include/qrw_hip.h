@@ -312,6 +312,47 @@ typedef struct {
 int qrw_iteration_bind(qrw_handle h, const qrw_iteration_buffers *buffers);
 int qrw_iteration_step(qrw_handle h, int32_t k, const double *d_x_f_mpc, void *stream);
 
+/* ---------------- state estimator: sensors in, filtered state out ----------------
+ * The stage of Controller.compute before everything above (scripts/Controller.py:213): Estimator.run_filter with the
+ * complementary filters (scripts/Estimator.py:466-629, kf_enabled = False as scripts/Controller.py:110-111 builds it), batched,
+ * with its per-instance state (contact counters, the two filters, yaw offset, call counter) in the handle.  Its outputs are the
+ * d_q_filt / d_v_filt / d_rpy / d_v_secu operands of qrw_controller_update_state, qrw_control_pre and qrw_iteration_bind: a
+ * sensors-in iteration is qrw_estimator_step writing into those buffers, followed by qrw_iteration_step or qrw_control_pre on the
+ * same stream.  Not provided: the Kalman variant (KFilter / KFilterBis), the logging arrays, plot_graphs.  One departure: the
+ * scan for `remaining_steps` (:476-479) stops at N_gait where the reference raises IndexError (every row equal to row 0). */
+typedef struct {
+  double h_init;   /* initial base height: FK_xyz[2] and the position filter's low-pass state (scripts/Estimator.py:279-283) */
+  int32_t perfect; /* perfectEstimator (:595-596, :601-602): base height and base-frame velocity taken from the true inputs   */
+} qrw_estimator_config;
+
+/* Replaces Estimator.__init__ (scripts/Estimator.py:245-342); dt is the handle's dt_wbc.  Resets the state: calling it again
+ * re-initialises (the yaw offset is latched again by the next two steps). */
+int qrw_estimator_init(qrw_handle h, const qrw_estimator_config *cfg, void *stream);
+
+/* Replaces Estimator.run_filter(k, gait, device, goals) (scripts/Estimator.py:466-629).  Only enqueues: no allocation, no
+ * synchronisation.
+ *   in : d_lin_acc [B][3] (device.baseLinearAcceleration), d_ang_vel [B][3] (baseAngularVelocity), d_quat [B][4] xyzw
+ *        (baseOrientation), d_q_mes [B][12], d_v_mes [B][12];
+ *        d_gait [B][N_gait][4] or NULL = the current gait of the handle's planner; d_goals [B][3][4] or NULL = its
+ *        FootTrajectoryGenerator::getFootPosition (item 9 of qrw_planner_get_host) -- NULL needs qrw_planner_init;
+ *        d_true_pos [B][3] (device.dummyPos) and d_true_b_vel [B][3] (device.b_baseVel): both given when the estimator was
+ *        initialised with perfect != 0, both NULL otherwise
+ *   out: d_q_filt [B][19], d_v_filt [B][18], d_rpy [B][3] (Estimator.RPY, yaw offset removed), d_v_secu [B][12] */
+int qrw_estimator_step(qrw_handle h, const double *d_lin_acc, const double *d_ang_vel, const double *d_quat,
+                       const double *d_q_mes, const double *d_v_mes, const double *d_gait, const double *d_goals,
+                       const double *d_true_pos, const double *d_true_b_vel, double *d_q_filt, double *d_v_filt,
+                       double *d_rpy, double *d_v_secu, void *stream);
+/* The same with host buffers, synchronised per handle (backs the single-robot drop-in Estimator.py). */
+int qrw_estimator_step_host(qrw_handle h, const double *h_lin_acc, const double *h_ang_vel, const double *h_quat,
+                            const double *h_q_mes, const double *h_v_mes, const double *h_gait, const double *h_goals,
+                            const double *h_true_pos, const double *h_true_b_vel, double *h_q_filt, double *h_v_filt,
+                            double *h_rpy, double *h_v_secu);
+
+/* Getter of estimator state items of instance b (count doubles): which = 0 k_since_contact (4), 1 FK_lin_vel (3), 2 FK_xyz (3),
+ * 3 xyz_mean_feet (3), 4 / 5 filter_xyz_vel HP_x / LP_x (3), 6 / 7 filter_xyz_pos HP_x / LP_x (3), 8 alpha, 9 close_from_contact,
+ * 10 offset_yaw_IMU, 11 k_log, 12 filt_lin_vel (3). */
+int qrw_estimator_get_host(qrw_handle h, int32_t which, int32_t b, int32_t count, double *h_out);
+
 /* ---------------- asynchronous MPC ----------------
  * The reference runs the MPC in a child process on its own CPU core and polls a shared flag
  * (scripts/MPC_Wrapper.py:150-298).  Here the MPC gets its own HIP stream restricted to a subset of the compute

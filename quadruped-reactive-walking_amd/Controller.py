@@ -3,9 +3,10 @@
 Mirrors `Controller.compute` of /root/reference/scripts/Controller.py:200-326 between the estimator output and the
 quantities sent to the control board: updateState -> Gait / FootstepPlanner / FootTrajectoryGenerator / StatePlanner
 -> MPC every k_mpc iterations -> WBC target assembly -> InvKin + QPWBC -> result + security_check.  Every stage is a
-HIP kernel of libqrw_hip.so working on the same handle; nothing leaves HBM.  The joystick, the state estimator, the
-PyBullet / masterboard devices and the loggers are outside the accelerated path: their outputs (reference velocity,
-filtered q / v, roll-pitch, joint velocities for the security check) are inputs here.
+HIP kernel of libqrw_hip.so working on the same handle; nothing leaves HBM.  The joystick, the PyBullet / masterboard
+devices and the loggers are outside the accelerated path.  compute() takes the state estimator's outputs (filtered q / v,
+roll-pitch-yaw, joint velocities for the security check) as inputs; with estimator=... the estimator runs on the device too
+(scripts/Controller.py:213) and compute_sensors() takes what the devices deliver: IMU and encoder readings.
 """
 import os
 import numpy as np
@@ -63,7 +64,7 @@ class Controller_batch:
 
     def __init__(self, batch, q_init, dt_wbc=0.002, dt_mpc=0.02, k_mpc=10, T_gait=0.32, T_mpc=0.32, N_gait=20,
                  h_ref=0.2229, device=0, multiprocessing=False, loop_cus=None, mpc_lag=None, fused=True, groups=None,
-                 stagger=None, deadline=None, _out_views=None):
+                 stagger=None, deadline=None, estimator=None, _out_views=None):
         """q_init: (12,) or (B,12) initial joint angles (Controller.__init__ q_init, scripts/Controller.py:60).
 
         groups: None or 1 = one handle (the default at every fleet size); G > 1 = the fleet as G stream groups
@@ -94,7 +95,11 @@ class Controller_batch:
         first iteration that finds its event complete (mpc_lag=None, what the reference's flag polling does), or --
         deterministic, for tests and replay -- exactly `mpc_lag` iterations after it was issued.
         The masked streams are ordinary (blocking) HIP streams: they synchronise with the legacy default stream, so call
-        compute() from a non-default stream (`with torch.cuda.stream(torch.cuda.Stream()): ...`) or the overlap is lost."""
+        compute() from a non-default stream (`with torch.cuda.stream(torch.cuda.Stream()): ...`) or the overlap is lost.
+
+        estimator=dict(h_init=..., perfect=False) (None = off, nothing changes): the state estimator on the device as well
+        (scripts/Estimator.py with the complementary filters, qrw_estimator_step), which enables compute_sensors(): IMU and
+        encoder readings in, Result out.  Its outputs live in the fleet-owned tensors q_filt / v_filt / rpy / v_secu."""
         import torch
 
         self._torch = torch
@@ -131,6 +136,7 @@ class Controller_batch:
         self.multiprocessing = bool(multiprocessing)
         self.mpc_lag = mpc_lag
         self._init_deadline(deadline)
+        self._init_estimator(estimator, None if _out_views is None else _out_views.get("estimator"))
         self.wbc_lanes = 16  # lanes per robot of the full WBC step (qrw_wbc_set_lanes): wbc16_kernel unless chosen otherwise below
         if self.multiprocessing:
             n_cu = qrw_hip.device_cu_count(device)
@@ -229,6 +235,60 @@ class Controller_batch:
             self._deadline_end(ev)
             return r
         return self._compute_any(joy_v_ref, q_filt, v_filt, rpy, v_secu, joystick_code)
+
+    # ---- sensors in: the state estimator in front of the iteration (scripts/Controller.py:213)
+    def _init_estimator(self, estimator, views=None):
+        """estimator: None (off) or dict(h_init=..., perfect=False).  views: a stream group's slices of the fleet's tensors."""
+        self.estimator = None if estimator is None else dict(h_init=float(estimator.get("h_init", 0.22294615)),
+                                                             perfect=bool(estimator.get("perfect", False)))
+        self.q_filt = self.v_filt = self.rpy = self.v_secu = None
+        if self.estimator is None:
+            return
+        unknown = set(estimator) - {"h_init", "perfect"}
+        if unknown:
+            raise qrw_hip.QrwError("estimator=: unknown keys %s (h_init, perfect)" % sorted(unknown))
+        torch = self._torch
+        if views is None:
+            mk = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.dev)
+            views = dict(q_filt=mk(self.B, 19), v_filt=mk(self.B, 18), rpy=mk(self.B, 3), v_secu=mk(self.B, 12))
+        # these four tensors never move: the bound iteration (_nonsolve_fast) recognises its inputs by identity
+        self._est_out = views
+        self.q_filt, self.v_filt, self.rpy, self.v_secu = views["q_filt"], views["v_filt"], views["rpy"], views["v_secu"]
+        if getattr(self, "_b", None) is not None:  # (Controller_groups: its groups' handles hold the state)
+            self._b.estimator_init(**self.estimator)
+            torch.cuda.current_stream(self.dev).synchronize()  # construction only: the steps may come on any other stream
+
+    def compute_sensors(self, joy_v_ref, lin_acc, ang_vel, quat, q_mes, v_mes, joystick_code=0, true_pos=None, true_b_vel=None):
+        """One control iteration from what a robot or a simulator delivers (needs estimator=... at construction): joy_v_ref (B,6),
+        lin_acc (B,3) IMU acceleration, ang_vel (B,3) gyro, quat (B,4) IMU orientation xyzw, q_mes / v_mes (B,12) encoders --
+        and true_pos / true_b_vel (B,3) for a perfect estimator; CUDA float64.  Estimator.run_filter (scripts/Controller.py:213)
+        on the stream the iteration runs on, with the gait and the foot positions of the handle's planner as the reference
+        passes them, into q_filt / v_filt / rpy / v_secu; then compute() on those.  Returns the Result views."""
+        if self.estimator is None:
+            raise qrw_hip.QrwError("compute_sensors needs the estimator: Controller_batch(..., estimator=dict(h_init=...))")
+        sensors = (lin_acc, ang_vel, quat, q_mes, v_mes, true_pos, true_b_vel)
+        if self.deadline is not None:
+            ev = self._deadline_begin()
+            r = self._sensors_any(joy_v_ref, sensors, joystick_code)
+            self._deadline_end(ev)
+            return r
+        return self._sensors_any(joy_v_ref, sensors, joystick_code)
+
+    def _sensors_any(self, joy_v_ref, sensors, joystick_code):
+        lin_acc, ang_vel, quat, q_mes, v_mes, true_pos, true_b_vel = sensors
+        step = lambda: self._b.estimator_step(lin_acc, ang_vel, quat, q_mes, v_mes, true_pos=true_pos, true_b_vel=true_b_vel,
+                                              out=self._est_out)
+        if self.multiprocessing:
+            # the iteration runs on the loop's stream (_compute_any): so does its estimator, after the caller's sensor writes
+            torch = self._torch
+            caller, loop = torch.cuda.current_stream(self.dev), self._s_loop.torch
+            if caller.cuda_stream != self._s_loop.ptr:
+                self._b.stream_wait_stream(loop, caller)
+            with torch.cuda.stream(loop):
+                step()
+        else:
+            step()
+        return self._compute_any(joy_v_ref, self.q_filt, self.v_filt, self.rpy, self.v_secu, joystick_code)
 
     def _compute_any(self, joy_v_ref, q_filt, v_filt, rpy, v_secu, joystick_code=0):
         if not self.multiprocessing:
@@ -425,7 +485,7 @@ class Controller_groups(Controller_batch):
 
     def __init__(self, batch, q_init, dt_wbc=0.002, dt_mpc=0.02, k_mpc=10, T_gait=0.32, T_mpc=0.32, N_gait=20,
                  h_ref=0.2229, device=0, multiprocessing=False, loop_cus=None, mpc_lag=None, fused=True, groups=None,
-                 stagger=None, deadline=None, _out_views=None):
+                 stagger=None, deadline=None, estimator=None, _out_views=None):
         import torch
 
         G = auto_groups(batch, groups, multiprocessing)
@@ -447,6 +507,7 @@ class Controller_groups(Controller_batch):
         self._delay = [(g * int(k_mpc)) // G if self.stagger else 0 for g in range(G)]
         self.lag = tuple(self._delay)  # fleet ticks group g runs behind group 0 (and holds q_init for at the start)
         self._init_deadline(deadline)
+        self._init_estimator(estimator)  # the fleet's q_filt / v_filt / rpy / v_secu; every group's handle steps its own slice
         self._calls = [0] * G
         self._views = None
         self._tick_ev = {}
@@ -472,7 +533,9 @@ class Controller_groups(Controller_batch):
                 self.groups.append(Controller_batch(
                     self.Bs, qi[sl], dt_wbc=dt_wbc, dt_mpc=dt_mpc, k_mpc=k_mpc, T_gait=T_gait, T_mpc=T_mpc, N_gait=N_gait,
                     h_ref=h_ref, device=device, multiprocessing=multiprocessing, loop_cus=loop_cus, mpc_lag=mpc_lag, fused=fused,
-                    groups=1, _out_views=dict(result=self._fleet_result[sl], error_flag=self.error_flag[sl])))
+                    groups=1, estimator=self.estimator,
+                    _out_views=dict(result=self._fleet_result[sl], error_flag=self.error_flag[sl],
+                                    estimator=None if self.estimator is None else {n: t[sl] for n, t in self._est_out.items()})))
 
     @property
     def loop_stream(self):
@@ -500,6 +563,16 @@ class Controller_groups(Controller_batch):
         `torch.cuda.stream(ctl.stream_of(g))`, once per fleet tick and group.  With stagger=True the first
         g * k_mpc / groups calls of group g do nothing (its robots have not started yet: its slice of the result holds q_init
         with the controller's PD gains, its error flags are 0) and return that slice."""
+        return self._group_tick(g, lambda c: c.compute(joy_v_ref, q_filt, v_filt, rpy, v_secu, joystick_code))
+
+    def compute_group_sensors(self, g, joy_v_ref, lin_acc, ang_vel, quat, q_mes, v_mes, joystick_code=0, true_pos=None,
+                              true_b_vel=None):
+        """compute_group from sensor readings (compute_sensors of group g alone; every argument is that group's slice).  A
+        staggered group's estimator starts with that group's first iteration: the calls before it do nothing."""
+        return self._group_tick(g, lambda c: c.compute_sensors(joy_v_ref, lin_acc, ang_vel, quat, q_mes, v_mes, joystick_code,
+                                                               true_pos, true_b_vel))
+
+    def _group_tick(self, g, iteration):
         torch = self._torch
         t = self._calls[g]
         self._calls[g] = t + 1
@@ -509,7 +582,7 @@ class Controller_groups(Controller_batch):
             return Result(self._fleet_result[self._sl[g]])
         if self.stagger and g > 0 and t == self._delay[g] and t in self._tick_ev:
             torch.cuda.current_stream(self.dev).wait_event(self._tick_ev[t])  # group 0 has finished its first t ticks
-        r = self.groups[g].compute(joy_v_ref, q_filt, v_filt, rpy, v_secu, joystick_code)
+        r = iteration(self.groups[g])
         if self.stagger and g == 0 and (t + 1) in self._delay[1:]:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.dev))
@@ -536,22 +609,30 @@ class Controller_groups(Controller_batch):
         iteration carries its MPC solve runs on the group's stream, forked from and joined to the caller's stream -- with
         staggered groups that is one group on two ticks out of k_mpc, and the fleet's worst tick takes a half-fleet solve instead
         of the whole fleet's."""
+        return self._fleet_tick((joy_v_ref, q_filt, v_filt, rpy, v_secu, joystick_code), self.compute_group)
+
+    def _sensors_any(self, joy_v_ref, sensors, joystick_code):
+        lin_acc, ang_vel, quat, q_mes, v_mes, true_pos, true_b_vel = sensors
+        return self._fleet_tick((joy_v_ref, lin_acc, ang_vel, quat, q_mes, v_mes, joystick_code, true_pos, true_b_vel),
+                                self.compute_group_sensors)
+
+    def _fleet_tick(self, args, group_call):
         torch = self._torch
         caller = torch.cuda.current_stream(self.dev)
-        views = self._group_views((joy_v_ref, q_filt, v_filt, rpy, v_secu, joystick_code))
+        views = self._group_views(args)
         if self.multiprocessing:
             forked = list(range(self.G))  # (asynchronous groups bring their own compute-unit-masked streams)
         else:
             forked = [g for g in range(self.G) if self._solves_now(g)]
             for g in range(self.G):
                 if g not in forked:
-                    self.compute_group(g, *views[g])
+                    group_call(g, *views[g])
         b0 = self.groups[0]._b
         for g in forked:
             st = self.streams[g]
             b0.stream_wait_stream(st, caller)  # the inputs produced on the caller's stream (and this tick's other groups) are ready
             with torch.cuda.stream(st):
-                self.compute_group(g, *views[g])
+                group_call(g, *views[g])
         for g in forked:
             b0.stream_wait_stream(caller, self.streams[g])
         return self.result

@@ -142,6 +142,7 @@ extern "C" int qrw_create(const qrw_config* cfg, qrw_handle* out) {
   zeroed(h->wbc_status, B, "qrw_create: hipMalloc wbc_status");
   zeroed(h->ctrl_st, B * (size_t)qrw::kCtrlStItems, "qrw_create: hipMalloc ctrl_st");
   zeroed(h->plan_st, B * (size_t)qrw::planner_state_items(cfg->N_gait), "qrw_create: hipMalloc plan_st");
+  zeroed(h->est_st, B * (size_t)qrw::kEstStItems, "qrw_create: hipMalloc est_st");
   // staging: the largest host-API call moves M (324) + Jc (216) + ... per instance
   zeroed(h->stage, B * (size_t)(12 * (N + 1) + cfg->N_gait * 12 + 24 * N + 1024), "qrw_create: hipMalloc stage");
   zeroed(h->stage_i, B, "qrw_create: hipMalloc stage_i");
@@ -170,12 +171,13 @@ extern "C" int qrw_destroy(qrw_handle h) {
   return 0;
 }
 
-// (the persistent solver state of the MPC and the WBC: not the diagnostics, planner, controller, staging or queue buffers)
+// (the persistent solver state of the MPC and the WBC and the estimator's filters: not the diagnostics, planner, controller,
+// staging or queue buffers)
 extern "C" int64_t qrw_state_bytes(qrw_handle h) {
   if (!h) return 0;
   return (int64_t)(h->mpc_st.bytes + h->mpc_gait.bytes + h->mpc_flags.bytes + h->mpc_iters.bytes + h->mpc_status.bytes +
                    h->mpc_rho_updates.bytes + h->mpc_order.bytes + h->mpc_ema.bytes + h->mpc_rho.bytes + h->mpc_pri.bytes +
-                   h->mpc_dua.bytes + h->wbc_st.bytes + h->wbc_iters.bytes + h->wbc_status.bytes);
+                   h->mpc_dua.bytes + h->wbc_st.bytes + h->wbc_iters.bytes + h->wbc_status.bytes + h->est_st.bytes);
 }
 
 // what every MPC launch of a handle is told about its persistent state; xref / fsteps / out as the caller lays them out
@@ -797,6 +799,98 @@ extern "C" int qrw_controller_result(qrw_handle h, const double* d_tau_ff, const
   a.in0 = d_tau_ff; a.in1 = d_qdes; a.in2 = d_vdes; a.in3 = d_q_filt; a.in4 = d_v_secu;
   a.out0 = d_result; a.iout = d_error_flag;
   return ctrl_launch(a, stream, "qrw_controller_result: launch failed");
+}
+
+// ------------------------------------------------------------------ state estimator (scripts/Estimator.py)
+// cut-off frequency -> first-order filter coefficient (scripts/Estimator.py:254-262)
+static double filter_alpha(double fc, double dt) {
+  const double y = 1 - cos(2 * M_PI * fc * dt);
+  return -y + sqrt(y * y + 2 * y);
+}
+static qrw::EstimatorArgs estimator_common(qrw_handle h) {
+  qrw::EstimatorArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = h->cfg.batch; a.N_gait = h->cfg.N_gait; a.perfect = h->ecfg.perfect ? 1 : 0;
+  a.dt = h->cfg.dt_wbc; a.h_init = h->ecfg.h_init; a.alpha_v = h->est_alpha_v; a.alpha_secu = h->est_alpha_secu;
+  a.es = h->est_st;
+  return a;
+}
+
+extern "C" int qrw_estimator_init(qrw_handle h, const qrw_estimator_config* cfg, void* stream) {
+  QRW_ENTER(h, !cfg, "qrw_estimator_init: null argument");
+  h->ecfg = *cfg;
+  h->est_alpha_v = filter_alpha(50.0, h->cfg.dt_wbc);
+  h->est_alpha_secu = filter_alpha(6.0, h->cfg.dt_wbc);
+  qrw::EstimatorArgs a = estimator_common(h);
+  a.init = 1;
+  if (qrw::estimator_launch(a, (hipStream_t)stream) != 0) return fail(-11, "qrw_estimator_init: launch failed", hipGetLastError());
+  note_launch(h, kFamEst, (hipStream_t)stream);
+  h->est_ready = true;
+  return 0;
+}
+
+extern "C" int qrw_estimator_step(qrw_handle h, const double* d_lin_acc, const double* d_ang_vel, const double* d_quat,
+                                  const double* d_q_mes, const double* d_v_mes, const double* d_gait, const double* d_goals,
+                                  const double* d_true_pos, const double* d_true_b_vel, double* d_q_filt, double* d_v_filt,
+                                  double* d_rpy, double* d_v_secu, void* stream) {
+  QRW_ENTER(h, !h->est_ready, "qrw_estimator_step: estimator not initialised");
+  if ((!d_gait || !d_goals) && !h->plan_ready)
+    return fail(-1, "qrw_estimator_step: planner not initialised (d_gait / d_goals NULL take the planner's gait and foot positions)");
+  if (!d_lin_acc || !d_ang_vel || !d_quat || !d_q_mes || !d_v_mes) return fail(-1, "qrw_estimator_step: null input");
+  if (!d_q_filt || !d_v_filt || !d_rpy || !d_v_secu) return fail(-1, "qrw_estimator_step: null output");
+  if (h->ecfg.perfect ? (!d_true_pos || !d_true_b_vel) : (d_true_pos || d_true_b_vel))
+    return fail(-1, h->ecfg.perfect ? "qrw_estimator_step: a perfect estimator needs both d_true_pos and d_true_b_vel"
+                                    : "qrw_estimator_step: d_true_pos / d_true_b_vel given to an estimator that is not perfect");
+  qrw::EstimatorArgs a = estimator_common(h);
+  a.lin_acc = d_lin_acc; a.ang_vel = d_ang_vel; a.quat = d_quat; a.q_mes = d_q_mes; a.v_mes = d_v_mes;
+  a.gait = d_gait; a.goals = d_goals; a.true_pos = d_true_pos; a.true_b_vel = d_true_b_vel;
+  a.ps = h->plan_st;
+  a.ps_cur = qrw::planner_item_offset(h->cfg.N_gait, 1);
+  a.ps_pos = qrw::planner_item_offset(h->cfg.N_gait, 9);
+  a.q_filt = d_q_filt; a.v_filt = d_v_filt; a.rpy = d_rpy; a.v_secu = d_v_secu;
+  if (qrw::estimator_launch(a, (hipStream_t)stream) != 0) return fail(-11, "qrw_estimator_step: launch failed", hipGetLastError());
+  note_launch(h, kFamEst, (hipStream_t)stream);
+  return 0;
+}
+
+extern "C" int qrw_estimator_step_host(qrw_handle h, const double* h_lin_acc, const double* h_ang_vel, const double* h_quat,
+                                       const double* h_q_mes, const double* h_v_mes, const double* h_gait, const double* h_goals,
+                                       const double* h_true_pos, const double* h_true_b_vel, double* h_q_filt, double* h_v_filt,
+                                       double* h_rpy, double* h_v_secu) {
+  QRW_ENTER_HOST(h, !h->est_ready, "qrw_estimator_step_host: estimator not initialised");
+  if (!h_lin_acc || !h_ang_vel || !h_quat || !h_q_mes || !h_v_mes) return fail(-1, "qrw_estimator_step_host: null input");
+  const size_t B = h->cfg.batch, Ng = h->cfg.N_gait;
+  HIP_OK(wait_family(h, kFamEst), "qrw_estimator_step_host: earlier estimator step of this handle");
+  if (!h_gait || !h_goals) HIP_OK(wait_family(h, kFamPlan), "qrw_estimator_step_host: earlier planner step of this handle");
+  Stager s(h);
+  const double *la = s.in(h_lin_acc, B * 3), *av = s.in(h_ang_vel, B * 3), *qt = s.in(h_quat, B * 4), *qm = s.in(h_q_mes, B * 12),
+               *vm = s.in(h_v_mes, B * 12);
+  const double* gt = h_gait ? s.in(h_gait, B * Ng * 4) : nullptr;
+  const double* gl = h_goals ? s.in(h_goals, B * 12) : nullptr;
+  const double* tp = h_true_pos ? s.in(h_true_pos, B * 3) : nullptr;
+  const double* tv = h_true_b_vel ? s.in(h_true_b_vel, B * 3) : nullptr;
+  double *qf = s.out(B * 19), *vf = s.out(B * 18), *rp = s.out(B * 3), *vs = s.out(B * 12);
+  if (!s.ok) return fail(-12, "qrw_estimator_step_host: staging failed");
+  if (const int rc = qrw_estimator_step(h, la, av, qt, qm, vm, gt, gl, tp, tv, qf, vf, rp, vs, (void*)h->host_stream)) return rc;
+  if (!(s.back(h_q_filt, qf, B * 19) && s.back(h_v_filt, vf, B * 18) && s.back(h_rpy, rp, B * 3) && s.back(h_v_secu, vs, B * 12)))
+    return fail(-12, "qrw_estimator_step_host: D2H failed");
+  HIP_OK(host_done(h), "qrw_estimator_step_host sync");
+  return 0;
+}
+
+extern "C" int qrw_estimator_get_host(qrw_handle h, int32_t which, int32_t b, int32_t count, double* h_out) {
+  QRW_ENTER_HOST(h, !h_out || b < 0 || b >= h->cfg.batch || count < 1, "qrw_estimator_get_host: bad argument");
+  static const int kOff[13] = {qrw::kEsKsc, qrw::kEsFkVel, qrw::kEsFkXyz, qrw::kEsMeanFeet, qrw::kEsHPv, qrw::kEsLPv, qrw::kEsHPp,
+                               qrw::kEsLPp, qrw::kEsAlpha, qrw::kEsClose, qrw::kEsYawOff, qrw::kEsKlog, qrw::kEsFiltVel};
+  static const int kLen[13] = {4, 3, 3, 3, 3, 3, 3, 3, 1, 1, 1, 1, 3};
+  if (which < 0 || which >= 13 || count > kLen[which]) return fail(-1, "qrw_estimator_get_host: bad item");
+  const size_t B = h->cfg.batch;
+  HIP_OK(wait_family(h, kFamEst), "qrw_estimator_get_host: earlier estimator step of this handle");
+  // (state items are [item][B]: one instance's items are B doubles apart)
+  HIP_OK(hipMemcpy2DAsync(h_out, sizeof(double), h->est_st + (size_t)kOff[which] * B + b, B * sizeof(double), sizeof(double), count,
+                          hipMemcpyDeviceToHost, h->host_stream), "qrw_estimator_get_host: D2H estimator state");
+  HIP_OK(host_done(h), "qrw_estimator_get_host: D2H estimator state");
+  return 0;
 }
 
 // ------------------------------------------------------------------ streams on a subset of the compute units

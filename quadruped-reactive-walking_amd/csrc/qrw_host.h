@@ -72,7 +72,7 @@ struct PinnedWord {
 
 // state families of a handle: which launches a getter has to wait for
 // (the controller-glue kernels write state no getter reads: their launches are not tracked)
-enum Family { kFamNone = -1, kFamMpc = 0, kFamWbc = 1, kFamPlan = 2, kFamCount = 3 };
+enum Family { kFamNone = -1, kFamMpc = 0, kFamWbc = 1, kFamPlan = 2, kFamEst = 3, kFamCount = 4 };
 
 }  // namespace qrw::host
 
@@ -111,14 +111,19 @@ struct qrw_handle_s {
   DevBuf<double> ctrl_st, plan_st;
   qrw_planner_config pcfg;
   bool plan_ready = false;
+  // state estimator
+  DevBuf<double> est_st;
+  qrw_estimator_config ecfg;
+  double est_alpha_v = 0.0, est_alpha_secu = 0.0;
+  bool est_ready = false;
   // staging for the host-buffer entry points
   DevBuf<double> stage;
   DevBuf<int32_t> stage_i;
   qrw_iteration_buffers iter_bufs;  // qrw_iteration_bind
   bool iter_bound = false;
   // (atomics: qrw_stream_destroy, called from whatever thread owns the stream, clears these in every live handle)
-  std::atomic<hipStream_t> last_stream[3] = {};
-  std::atomic<bool> launched[3] = {};
+  std::atomic<hipStream_t> last_stream[qrw::host::kFamCount] = {};
+  std::atomic<bool> launched[qrw::host::kFamCount] = {};
   // host_stream drains before the members above free their buffers (the zero fills of a creation that failed half-way run on it)
   ~qrw_handle_s() {
     if (host_stream) { (void)hipStreamSynchronize(host_stream); (void)hipStreamDestroy(host_stream); }

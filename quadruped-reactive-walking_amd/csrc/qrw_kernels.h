@@ -176,4 +176,37 @@ int control_pre_launch(const ControllerArgs& cu, const PlannerArgs& p, const Con
                        hipStream_t stream);
 int planner_item_offset(int N_gait, int which);
 int planner_launch(const PlannerArgs& a, hipStream_t stream);
+
+// ---- state estimator (estimator_kernel.hip)
+// persistent state: es[item][B] (item-major, as the controller glue's CS: a wavefront's loads of one item coalesce)
+enum EstStateItem {
+  kEsKsc = 0,        // k_since_contact (4)
+  kEsFkVel = 4,      // FK_lin_vel (3)
+  kEsFkXyz = 7,      // FK_xyz (3)
+  kEsMeanFeet = 10,  // xyz_mean_feet (3)
+  kEsHPv = 13,       // filter_xyz_vel.HP_x (3)
+  kEsLPv = 16,       // filter_xyz_vel.LP_x (3)
+  kEsHPp = 19,       // filter_xyz_pos.HP_x (3)
+  kEsLPp = 22,       // filter_xyz_pos.LP_x (3)
+  kEsAlpha = 25,
+  kEsClose = 26,     // close_from_contact
+  kEsYawOff = 27,    // offset_yaw_IMU
+  kEsKlog = 28,
+  kEsFiltVel = 29,   // filt_lin_vel (3)
+  kEsVfilt = 32,     // v_filt[0:3] of the previous call (3)
+  kEsVsecu = 35,     // v_secu of the previous call (12)
+  kEstStItems = 47
+};
+struct EstimatorArgs {
+  int B, N_gait, init, perfect;
+  double dt, h_init, alpha_v, alpha_secu;
+  const double *lin_acc, *ang_vel, *quat, *q_mes, *v_mes;  // [B][3], [B][3], [B][4] xyzw, [B][12], [B][12]
+  const double *gait, *goals;                              // [B][N_gait][4], [B][3][4]; null = the planner state below
+  const double* ps;                                        // planner state [item][B]
+  int ps_cur, ps_pos;                                      // its items "current gait" (4 column masks) and "foot position" (12)
+  const double *true_pos, *true_b_vel;                     // perfect estimator: [B][3] each
+  double *q_filt, *v_filt, *rpy, *v_secu;                  // [B][19], [B][18], [B][3], [B][12]
+  double* es;                                              // [kEstStItems][B]
+};
+int estimator_launch(const EstimatorArgs& a, hipStream_t stream);
 }

@@ -28,6 +28,16 @@ class _PlannerConfig(C.Structure):
                 ("lock_time", C.c_double), ("init_target", C.c_double * 12), ("init_foot_pos", C.c_double * 12)]
 
 
+class _EstimatorConfig(C.Structure):
+    _fields_ = [("h_init", C.c_double), ("perfect", C.c_int32)]
+
+
+# qrw_estimator_get_host: item -> (which, count)
+ESTIMATOR_ITEMS = {"k_since_contact": (0, 4), "FK_lin_vel": (1, 3), "FK_xyz": (2, 3), "xyz_mean_feet": (3, 3),
+                   "HP_lin_vel": (4, 3), "LP_lin_vel": (5, 3), "HP_lin_pos": (6, 3), "LP_lin_pos": (7, 3), "alpha": (8, 1),
+                   "close_from_contact": (9, 1), "offset_yaw_IMU": (10, 1), "k_log": (11, 1), "filt_lin_vel": (12, 3)}
+
+
 class _IterationBuffers(C.Structure):
     """qrw_iteration_buffers (include/qrw_hip.h), field for field."""
     _fields_ = ([(n, C.c_void_p) for n in ("d_joy_vref", "d_q_filt", "d_v_filt", "d_rpy", "d_v_secu", "d_code")]
@@ -86,6 +96,10 @@ SIGNATURES = {
     "qrw_wbc_compute_result": (C.c_int, [_vp] + [_vp] * 13 + [_vp] * 4 + [_vp]),
     "qrw_iteration_bind": (C.c_int, [_vp, C.POINTER(_IterationBuffers)]),
     "qrw_iteration_step": (C.c_int, [_vp, C.c_int32, _vp, _vp]),
+    "qrw_estimator_init": (C.c_int, [_vp, _vp, _vp]),
+    "qrw_estimator_step": (C.c_int, [_vp] + [_vp] * 13 + [_vp]),
+    "qrw_estimator_step_host": (C.c_int, [_vp] + [_dp] * 13),
+    "qrw_estimator_get_host": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "qrw_stream_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
     "qrw_stream_destroy": (C.c_int, [_vp]),
     "qrw_device_cu_count": (C.c_int, [C.c_int32, _ip]),
@@ -608,6 +622,52 @@ class Batch:
                 _check(rc, "qrw_iteration_step")
 
         return step
+
+    # ------------------------------------------------ state estimator (scripts/Estimator.py, complementary filters)
+    def estimator_init(self, h_init=0.22294615, perfect=False):
+        """Estimator.__init__ (scripts/Estimator.py:245-342) for every instance; again = re-initialise."""
+        ec = _EstimatorConfig(float(h_init), int(bool(perfect)))
+        _check(self._lib.qrw_estimator_init(self._handle, C.cast(C.byref(ec), _vp), self._stream()), "qrw_estimator_init")
+        self.estimator_perfect = bool(perfect)
+
+    def estimator_step(self, lin_acc, ang_vel, quat, q_mes, v_mes, gait=None, goals=None, true_pos=None, true_b_vel=None,
+                       out=None):
+        """Estimator.run_filter (scripts/Estimator.py:466-629) on CUDA float64 tensors: lin_acc (B,3), ang_vel (B,3), quat (B,4)
+        xyzw, q_mes (B,12), v_mes (B,12); gait (B,N_gait,4) / goals (B,3,4), or None = the handle's planner state; true_pos /
+        true_b_vel (B,3) for a perfect estimator.  Returns dict (q_filt, v_filt, rpy, v_secu); only enqueues."""
+        import torch
+
+        B = self.B
+        if out is None:
+            mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=q_mes.device)
+            out = dict(q_filt=mk(B, 19), v_filt=mk(B, 18), rpy=mk(B, 3), v_secu=mk(B, 12))
+        d = self._dev
+        opt = lambda t, shape: _vp(0) if t is None else d(t, shape)
+        _check(self._lib.qrw_estimator_step(
+            self._handle, d(lin_acc, (B, 3)), d(ang_vel, (B, 3)), d(quat, (B, 4)), d(q_mes, (B, 12)), d(v_mes, (B, 12)),
+            opt(gait, (B, self.N_gait, 4)), opt(goals, (B, 3, 4)), opt(true_pos, (B, 3)), opt(true_b_vel, (B, 3)),
+            d(out["q_filt"], (B, 19)), d(out["v_filt"], (B, 18)), d(out["rpy"], (B, 3)), d(out["v_secu"], (B, 12)),
+            self._stream()), "qrw_estimator_step")
+        return out
+
+    def estimator_step_host(self, lin_acc, ang_vel, quat, q_mes, v_mes, gait=None, goals=None, true_pos=None, true_b_vel=None):
+        """The same with numpy arrays (qrw_estimator_step_host): what the single-robot drop-in Estimator.py uses."""
+        B = self.B
+        opt = lambda x, shape: None if x is None else _h(x, shape)
+        a = [_h(lin_acc, (B, 3)), _h(ang_vel, (B, 3)), _h(quat, (B, 4)), _h(q_mes, (B, 12)), _h(v_mes, (B, 12)),
+             opt(gait, (B, self.N_gait, 4)), opt(goals, (B, 3, 4)), opt(true_pos, (B, 3)), opt(true_b_vel, (B, 3))]
+        o = dict(q_filt=np.empty((B, 19)), v_filt=np.empty((B, 18)), rpy=np.empty((B, 3)), v_secu=np.empty((B, 12)))
+        _check(self._lib.qrw_estimator_step_host(self._handle, *[_p(x) for x in a], _p(o["q_filt"]), _p(o["v_filt"]),
+                                                 _p(o["rpy"]), _p(o["v_secu"])), "qrw_estimator_step_host")
+        return o
+
+    def estimator_get(self, item, b=0):
+        """One estimator state item of instance b (ESTIMATOR_ITEMS: k_since_contact, FK_lin_vel, FK_xyz, xyz_mean_feet, the HP /
+        LP halves of both filters, alpha, close_from_contact, offset_yaw_IMU, k_log, filt_lin_vel) as a numpy array."""
+        which, count = ESTIMATOR_ITEMS[item]
+        out = np.empty(count)
+        _check(self._lib.qrw_estimator_get_host(self._handle, which, int(b), count, _p(out)), "qrw_estimator_get_host")
+        return out
 
     # ------------------------------------------------ getters / diagnostics
     def mpc_gait(self, b=0):

@@ -425,3 +425,40 @@ class RandomWbcInputs:
             vg[b] = r.uniform(-1.0, 1.0, (3, 4)) * (1 - ct)[None, :]
             ag[b] = r.uniform(-10.0, 10.0, (3, 4)) * (1 - ct)[None, :]
         return dict(q=q, dq=dq, f_cmd=f, contacts=self.contacts.copy(), pgoals=pg, vgoals=vg, agoals=ag)
+
+
+class SyntheticSensors:
+    """Seeded per-tick sensor readings of B robots, what a robot or a simulator delivers to the state estimator
+    (scripts/Estimator.py:347-385): a small random attitude (roll / pitch within +-0.05 rad, yaw wandering +-0.1 rad around an
+    arbitrary CONSTANT yaw offset per robot, which the estimator has to remove), gyro within +-0.3 rad/s, gravity-debiased
+    acceleration within +-0.5 m/s^2, joint angles within +-0.05 rad of Q_NOMINAL moving smoothly (sinusoids of random phase, so
+    that the joint velocities are their bounded derivatives, below 2 rad/s).  step(k) -> dict(lin_acc (B,3), ang_vel (B,3),
+    quat (B,4) xyzw, q_mes (B,12), v_mes (B,12)); the same k gives the same readings."""
+
+    def __init__(self, B, seed=20800000, dt=0.002):
+        self.B, self.dt = int(B), float(dt)
+        r = np.random.default_rng(seed)
+        self.yaw0 = r.uniform(-np.pi, np.pi, B)
+        self.amp = r.uniform(0.01, 0.05, (B, 12))
+        self.freq = r.uniform(1.0, 6.0, (B, 12))  # Hz: |v| <= 2 pi 6 * 0.05 < 2 rad/s
+        self.phase = r.uniform(0.0, 2 * np.pi, (B, 12))
+        self.att_amp = r.uniform(0.0, 1.0, (B, 3)) * np.array([0.05, 0.05, 0.1])
+        self.att_freq = r.uniform(0.5, 2.0, (B, 3))
+        self.att_phase = r.uniform(0.0, 2 * np.pi, (B, 3))
+        self.seed = int(seed)
+
+    def step(self, k):
+        t = k * self.dt
+        r = np.random.default_rng([self.seed, int(k)])
+        w = 2 * np.pi * self.freq
+        q_mes = Q_NOMINAL[None, :] + self.amp * np.sin(w * t + self.phase)
+        v_mes = self.amp * w * np.cos(w * t + self.phase)
+        rpy = self.att_amp * np.sin(2 * np.pi * self.att_freq * t + self.att_phase)
+        rpy[:, 2] += self.yaw0
+        sr, cr = np.sin(rpy[:, 0] / 2), np.cos(rpy[:, 0] / 2)
+        sp, cp = np.sin(rpy[:, 1] / 2), np.cos(rpy[:, 1] / 2)
+        sy, cy = np.sin(rpy[:, 2] / 2), np.cos(rpy[:, 2] / 2)
+        quat = np.stack([sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy,
+                         cr * cp * cy + sr * sp * sy], 1)
+        return dict(lin_acc=r.uniform(-0.5, 0.5, (self.B, 3)), ang_vel=r.uniform(-0.3, 0.3, (self.B, 3)), quat=quat,
+                    q_mes=q_mes, v_mes=v_mes)
