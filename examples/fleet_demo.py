@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """A fleet of Solo12 robots stepped by the device-resident control loop, paced at the reference's 2 ms (src/config_solo12.yaml:6).
 
-    python examples/fleet_demo.py [robots] [seconds] [sync|async|auto] [--sensors]
+    python examples/fleet_demo.py [robots] [seconds] [sync|async|auto] [--sensors | --sim] [--vx=V]
 
 `Controller_batch` mirrors `Controller.compute` of the reference (scripts/Controller.py:200-326) for B robots: the estimator's
 outputs go in (reference velocity, filtered q / v, roll-pitch, joint velocities), the PD targets and feed-forward torques come out;
 everything in between -- planners, the MPC every k_mpc-th tick, the whole-body controller, the security check -- runs in HBM.
 Here a perfect actuator stands in for the robots (the next tick's measured joints are this tick's targets).
 With --sensors the estimator runs on the device too (Controller_batch(..., estimator=...).compute_sensors): what goes in is what a
-robot delivers -- IMU acceleration, gyro, IMU orientation, encoder angles and velocities, here synthetic (synth.SyntheticSensors)."""
+robot delivers -- IMU acceleration, gyro, IMU orientation, encoder angles and velocities, here synthetic (synth.SyntheticSensors).
+With --sim the loop is closed: a simulated robot per controller (Simulator.Simulator_batch: forward dynamics with penalty contact on
+a flat plane, one more kernel per tick) takes the PD targets and torques and delivers the next readings; at the end the robots
+without an error flag and without a simulator status are counted and the distance they covered is printed.  --vx=V gives every
+robot the forward reference speed V and no yaw rate (default: 0 to 0.4 m/s and -0.3 to 0.3 rad/s, drawn per robot)."""
 import os
 import sys
 import time
@@ -20,13 +24,16 @@ import torch  # noqa: E402
 
 import synth  # noqa: E402
 from Controller import Controller_batch  # noqa: E402
+from Simulator import Simulator_batch  # noqa: E402
 
-sensors = "--sensors" in sys.argv
-argv = [a for a in sys.argv if a != "--sensors"]
+sim_on = "--sim" in sys.argv
+sensors = "--sensors" in sys.argv and not sim_on
+vx = [float(a[5:]) for a in sys.argv if a.startswith("--vx=")]
+argv = [a for a in sys.argv if a not in ("--sensors", "--sim") and not a.startswith("--vx=")]
 B = int(argv[1]) if len(argv) > 1 else 1024
 seconds = float(argv[2]) if len(argv) > 2 else 1.0
 mode = argv[3] if len(argv) > 3 else "sync"
-est = dict(h_init=0.22294615) if sensors else None  # (scripts/Estimator.py:245)
+est = dict(h_init=0.22294615) if (sensors or sim_on) else None  # (scripts/Estimator.py:245)
 dev = torch.device("cuda", 0)
 q_init = np.array([0.0, 0.7, -1.4, -0.0, 0.7, -1.4, 0.0, -0.7, +1.4, -0.0, -0.7, +1.4])  # scripts/main_solo12_control.py:120
 
@@ -42,6 +49,8 @@ with torch.cuda.stream(torch.cuda.Stream(dev)):  # (keep the caller's work off t
         rng = np.random.default_rng(0)
         v = np.zeros((B, 6))
         v[:, 0], v[:, 5] = rng.uniform(0.0, 0.4, B), rng.uniform(-0.3, 0.3, B)  # forward speed, yaw rate (the joystick's output)
+        if vx:
+            v[:, 0], v[:, 5] = vx[0], 0.0
         v_ref = torch.from_numpy(v).to(dev)
         q_filt = torch.zeros((B, 19), dtype=torch.float64, device=dev)
         q_filt[:, 2], q_filt[:, 6] = 0.2229, 1.0
@@ -53,13 +62,17 @@ with torch.cuda.stream(torch.cuda.Stream(dev)):  # (keep the caller's work off t
         sen = synth.SyntheticSensors(B, 0) if sensors else None
         names = ("lin_acc", "ang_vel", "quat", "q_mes", "v_mes")
         s_dev = {n: torch.empty(v.shape, dtype=torch.float64, device=dev) for n, v in sen.step(0).items()} if sensors else None
+        sim = Simulator_batch(B, q_init, controller=ctl) if sim_on else None
         lat, nxt = [], time.perf_counter()
         for k in range(int(seconds / 0.002)):
             while time.perf_counter() < nxt:
                 pass
             nxt = max(nxt + 0.002, time.perf_counter())
             t0 = time.perf_counter()
-            if sensors:
+            if sim_on:
+                r = ctl.compute_sensors(v_ref, **sim.sensors)            # estimator + control iteration on the simulator's readings
+                sim.step(r)                                             # SendCommand + the next UpdateMeasurment
+            elif sensors:
                 for n, v in sen.step(k).items():                    # this tick's readings into the fixed input tensors
                     s_dev[n].copy_(torch.from_numpy(v))
                 r = ctl.compute_sensors(v_ref, *[s_dev[n] for n in names])
@@ -71,9 +84,22 @@ with torch.cuda.stream(torch.cuda.Stream(dev)):  # (keep the caller's work off t
             lat.append(1e3 * (time.perf_counter() - t0))
         stopped = int((ctl.error_flag != 0).sum().item())
         tau = float(r.tau_ff.abs().max().item())
+        if sim_on:
+            st, flags = sim.state(), ctl.error_flag.cpu().numpy()
+            good = (flags == 0) & (st["status"] == 0)
+            fell = int((st["q"][good, 2] < 0.12).sum())
+            sim_line = ("; closed loop: %d of %d robots end with error_flag 0 and simulator status 0 (error flags set %d %s, frozen %d); of those, "
+                        "%d have the base below 0.12 m; base height median %.3f m, distance covered in x median %.3f m (min %.3f, max %.3f) in "
+                        "%.2f s at reference speeds %.2f..%.2f m/s"
+                        % (int(good.sum()), B, int((flags != 0).sum()), dict(zip(*[x.tolist() for x in np.unique(flags, return_counts=True)])),
+                           int((st["status"] != 0).sum()), fell,
+                           float(np.median(st["q"][good, 2])) if good.any() else float("nan"),
+                           *(([float(f(st["q"][good, 0])) for f in (np.median, np.min, np.max)]) if good.any() else [float("nan")] * 3),
+                           0.002 * (k + 1), v[:, 0].min(), v[:, 0].max()))
     ctl.stop_parallel_loop()
 lat = np.array(lat)
 warm = lat[20:]  # the first two MPC solves start cold (QP set-up, ~1 000 ADMM iterations): like the reference's first iterations
 print("%d robots, %s mode%s, %d ticks paced at 2 ms: tick latency median %.3f ms, worst %.3f ms after the first 20 ticks (%d ticks over the slot; "
-      "cold start: %.3f ms); largest |tau_ff| %.2f N m; robots in security stop %d"
-      % (B, mode, ", sensors in" if sensors else "", len(lat), np.median(lat), warm.max(), int((warm > 2.0).sum()), lat[:20].max(), tau, stopped))
+      "cold start: %.3f ms); largest |tau_ff| %.2f N m; robots in security stop %d%s"
+      % (B, mode, ", simulator in the loop" if sim_on else ", sensors in" if sensors else "", len(lat), np.median(lat), warm.max(),
+         int((warm > 2.0).sum()), lat[:20].max(), tau, stopped, sim_line if sim_on else ""))

@@ -353,6 +353,59 @@ int qrw_estimator_step_host(qrw_handle h, const double *h_lin_acc, const double 
  * 10 offset_yaw_IMU, 11 k_log, 12 filt_lin_vel (3). */
 int qrw_estimator_get_host(qrw_handle h, int32_t which, int32_t b, int32_t count, double *h_out);
 
+/* ---------------- rigid-body simulator: torques in, sensor readings out ----------------
+ * What closes the loop around the controller: per instance one Solo12 on a flat plane, stepped on the device.  One tick is the
+ * reference's SendCommand followed by the next UpdateMeasurment (scripts/PyBulletSimulator.py:672-710, :588-633): the PD+ law
+ * tau = tau_ff + P (q_des - q) + D (v_des - dq) from the joint state at the start of the tick, held over `substeps` semi-implicit
+ * Euler steps of the forward dynamics, then the readings qrw_estimator_step takes, in its layouts.  The physics is NOT
+ * PyBullet's: penalty contact (fn = max(0, kn d - dn vz) while the penetration d = foot_radius - z_foot > 0, friction
+ * -mu fn v_t / sqrt(|v_t|^2 + vs^2)) on the plane z = 0 only; no joint limits, no joint friction, no motor model.
+ * State per instance, QRW_SIM_STATE_ITEMS doubles: q19 (position, quaternion xyzw, joints FL FR HL HR), v18 (base linear and
+ * angular velocity in the base frame, joint velocities), prev_o_imuVel (3), tick counter, status.  A robot whose new state is not
+ * finite gets status 1 and is frozen: nothing of that tick or a later one is stored for it (its rows of the output buffers keep
+ * what the last finite tick wrote); the others are unaffected. */
+#define QRW_SIM_STATE_ITEMS 42
+typedef struct {
+  double dt;           /* tick (0.002, the controller's dt_wbc)                                  */
+  int32_t substeps;    /* >= 1 (8)                                                               */
+  double kn, dn;       /* normal stiffness N/m (1e4) and damping N s/m (60)                      */
+  double mu, vs;       /* friction coefficient (0.9) and regularisation velocity m/s (0.01)      */
+  double foot_radius;  /* 0.0155 (scripts/Estimator.py:596)                                      */
+  double base_height;  /* base height of qrw_sim_init with q_ld = 12 (0.2596: feet resting at 0.7 / -1.4) */
+} qrw_sim_params;
+/* device output buffers of a tick: the first five are the inputs of qrw_estimator_step, d_true_pos / d_true_b_vel those of a
+ * perfect estimator (dummyPos, b_baseVel); d_o_imu_vel is o_imuVel, d_contact_forces the world forces on the feet in the last
+ * sub-step, d_joint_torques the tick's tau.  None may be NULL. */
+typedef struct {
+  double *d_q_mes, *d_v_mes;      /* [B][12] */
+  double *d_quat;                 /* [B][4] xyzw */
+  double *d_ang_vel, *d_lin_acc;  /* [B][3] base frame (baseAngularVelocity, baseLinearAcceleration) */
+  double *d_o_imu_vel, *d_true_pos, *d_true_b_vel; /* [B][3] */
+  double *d_contact_forces;       /* [B][4][3] */
+  double *d_joint_torques;        /* [B][12] */
+} qrw_sim_buffers;
+
+/* Sets the state (d_q_init [B][q_ld]: q_ld = 19 the whole q19, q_ld = 12 the joints with the base level at params->base_height;
+ * velocities, prev_o_imuVel, tick and status zero) and writes the first measurement, as the reference's first UpdateMeasurment.
+ * Again = re-initialise. */
+int qrw_sim_init(qrw_handle h, const double *d_q_init, int32_t q_ld, const qrw_sim_params *params, const qrw_sim_buffers *out,
+                 void *stream);
+/* One tick.  d_P, d_D, d_q_des, d_v_des, d_tau_ff: rows of 12 per instance, cmd_ld doubles apart (12 for five plain [B][12]
+ * buffers, 60 for the five planes of a qrw_controller_result [B][5][12]); d_f_ext [B][6] a world force and moment at the base
+ * origin, or NULL.  Only enqueues. */
+int qrw_sim_step(qrw_handle h, const double *d_P, const double *d_D, const double *d_q_des, const double *d_v_des,
+                 const double *d_tau_ff, int32_t cmd_ld, const double *d_f_ext, const qrw_sim_buffers *out, void *stream);
+/* The same two with host buffers ([B][q_ld] initial configuration, [B][12] commands, h_f_ext [B][6] or NULL; h_out holds HOST
+ * pointers, NULL = not wanted), synchronised per handle (they back the single-robot drop-in PyBulletSimulator.py).  The
+ * measurements live in device buffers the handle allocates at the first qrw_sim_init_host; qrw_sim_step_host needs that call. */
+int qrw_sim_init_host(qrw_handle h, const double *h_q_init, int32_t q_ld, const qrw_sim_params *params, const qrw_sim_buffers *h_out);
+int qrw_sim_step_host(qrw_handle h, const double *h_P, const double *h_D, const double *h_q_des, const double *h_v_des,
+                      const double *h_tau_ff, const double *h_f_ext, const qrw_sim_buffers *h_out);
+/* The whole state, [QRW_SIM_STATE_ITEMS][batch] (item-major, as the device holds it): for tests and restarts.  Setting it does
+ * not rewrite the measurement buffers. */
+int qrw_sim_get_host(qrw_handle h, double *h_state);
+int qrw_sim_set_host(qrw_handle h, const double *h_state);
+
 /* ---------------- asynchronous MPC ----------------
  * The reference runs the MPC in a child process on its own CPU core and polls a shared flag
  * (scripts/MPC_Wrapper.py:150-298).  Here the MPC gets its own HIP stream restricted to a subset of the compute

@@ -1,6 +1,6 @@
 /*
  * include/qrw_hip_test.h -- entry points of libqrw_hip.so that exist for the TEST SUITE only (fault injection, register / LDS
- * poisoning).  Not part of the drop-in boundary: nothing a caller of the reference's interfaces needs is declared here, and a
+ * poisoning, the simulator's forward dynamics alone).  Not part of the drop-in boundary: nothing a caller of the reference's interfaces needs is declared here, and a
  * deployment has no reason to include this file.  The product surface is include/qrw_hip.h.
  */
 #ifndef QRW_HIP_TEST_H_
@@ -26,6 +26,14 @@ int qrw_test_known_answer(int32_t N, int32_t mode, uint64_t lds_pattern, int32_t
 /* Tests only: after the LDS / register-file fills of qrw_test_known_answer, what a new wavefront finds in an LDS word, v255 and a255
  * it has not written: h_out3[0..2], all-ones when the fills are effective on this device. */
 int qrw_test_poison_probe(uint32_t *h_out3);
+
+/* Tests only: the rigid-body simulator's forward dynamics alone (csrc/sim_dynamics.h), the piece that is held directly against the
+ * CPU oracle: for n states (h_q19 [n][19], h_v18 [n][18]) under the joint torques h_tau12 [n][12] and the optional world wrench
+ * h_f_ext [n][6] at the base origin, the accelerations h_a18 [n][18] of M(q) a = [0; tau] + J'f + wrench - h(q, v) and the contact
+ * forces h_contact_forces [n][4][3] (world) of the penalty law with params' kn, dn, mu, vs, foot_radius.  Host buffers; the
+ * handle only names the device. */
+int qrw_test_sim_forward_dynamics(qrw_handle h, int32_t n, const double *h_q19, const double *h_v18, const double *h_tau12,
+                                  const double *h_f_ext, const qrw_sim_params *params, double *h_a18, double *h_contact_forces);
 
 #ifdef __cplusplus
 }

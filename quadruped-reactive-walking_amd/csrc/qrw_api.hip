@@ -177,7 +177,7 @@ extern "C" int64_t qrw_state_bytes(qrw_handle h) {
   if (!h) return 0;
   return (int64_t)(h->mpc_st.bytes + h->mpc_gait.bytes + h->mpc_flags.bytes + h->mpc_iters.bytes + h->mpc_status.bytes +
                    h->mpc_rho_updates.bytes + h->mpc_order.bytes + h->mpc_ema.bytes + h->mpc_rho.bytes + h->mpc_pri.bytes +
-                   h->mpc_dua.bytes + h->wbc_st.bytes + h->wbc_iters.bytes + h->wbc_status.bytes + h->est_st.bytes);
+                   h->mpc_dua.bytes + h->wbc_st.bytes + h->wbc_iters.bytes + h->wbc_status.bytes + h->est_st.bytes + h->sim_st.bytes);
 }
 
 // what every MPC launch of a handle is told about its persistent state; xref / fsteps / out as the caller lays them out
@@ -890,6 +890,140 @@ extern "C" int qrw_estimator_get_host(qrw_handle h, int32_t which, int32_t b, in
   HIP_OK(hipMemcpy2DAsync(h_out, sizeof(double), h->est_st + (size_t)kOff[which] * B + b, B * sizeof(double), sizeof(double), count,
                           hipMemcpyDeviceToHost, h->host_stream), "qrw_estimator_get_host: D2H estimator state");
   HIP_OK(host_done(h), "qrw_estimator_get_host: D2H estimator state");
+  return 0;
+}
+
+// ------------------------------------------------------------------ rigid-body simulator (sim_kernel.hip)
+static const char* sim_bad_params(const qrw_sim_params* p) {
+  if (!(p->dt > 0.0) || p->substeps < 1 || p->substeps > 1024) return "dt must be > 0 and substeps in 1..1024";
+  if (!(p->kn >= 0.0) || !(p->dn >= 0.0) || !(p->mu >= 0.0) || !(p->vs > 0.0)) return "kn, dn, mu must be >= 0 and vs > 0";
+  return nullptr;
+}
+static bool sim_buffers_complete(const qrw_sim_buffers* o) {
+  return o && o->d_q_mes && o->d_v_mes && o->d_quat && o->d_ang_vel && o->d_lin_acc && o->d_o_imu_vel && o->d_true_pos && o->d_true_b_vel &&
+         o->d_contact_forces && o->d_joint_torques;
+}
+static qrw::SimArgs sim_common(qrw_handle h, int mode, const qrw_sim_buffers* o) {
+  qrw::SimArgs a;
+  memset(&a, 0, sizeof(a));
+  const qrw_sim_params& p = h->sim_prm;
+  a.B = h->cfg.batch; a.mode = mode; a.substeps = p.substeps; a.cmd_ld = 12; a.q_ld = 19;
+  a.dt = p.dt; a.kn = p.kn; a.dn = p.dn; a.mu = p.mu; a.vs = p.vs; a.foot_radius = p.foot_radius; a.base_height = p.base_height;
+  a.ss = h->sim_st;
+  a.q_mes = o->d_q_mes; a.v_mes = o->d_v_mes; a.quat = o->d_quat; a.ang_vel = o->d_ang_vel; a.lin_acc = o->d_lin_acc;
+  a.o_imu_vel = o->d_o_imu_vel; a.true_pos = o->d_true_pos; a.true_b_vel = o->d_true_b_vel;
+  a.contact_forces = o->d_contact_forces; a.joint_torques = o->d_joint_torques;
+  return a;
+}
+// the handle's own measurement buffers (host-buffer entry points), carved out of sim_out
+static qrw_sim_buffers sim_own_buffers(qrw_handle h) {
+  const size_t B = h->cfg.batch;
+  double* p = h->sim_out;
+  qrw_sim_buffers o;
+  o.d_q_mes = p; p += B * 12;
+  o.d_v_mes = p; p += B * 12;
+  o.d_quat = p; p += B * 4;
+  o.d_ang_vel = p; p += B * 3;
+  o.d_lin_acc = p; p += B * 3;
+  o.d_o_imu_vel = p; p += B * 3;
+  o.d_true_pos = p; p += B * 3;
+  o.d_true_b_vel = p; p += B * 3;
+  o.d_contact_forces = p; p += B * 12;
+  o.d_joint_torques = p;
+  return o;
+}
+constexpr size_t kSimOutPerInstance = 12 + 12 + 4 + 3 * 5 + 12 + 12;
+static int sim_read_own(qrw_handle h, const qrw_sim_buffers* ho, const char* who) {
+  const size_t B = h->cfg.batch;
+  const qrw_sim_buffers d = sim_own_buffers(h);
+  return read_back(h, kFamNone, who,
+                   {{ho->d_q_mes, d.d_q_mes, B * 12 * sizeof(double)}, {ho->d_v_mes, d.d_v_mes, B * 12 * sizeof(double)},
+                    {ho->d_quat, d.d_quat, B * 4 * sizeof(double)}, {ho->d_ang_vel, d.d_ang_vel, B * 3 * sizeof(double)},
+                    {ho->d_lin_acc, d.d_lin_acc, B * 3 * sizeof(double)}, {ho->d_o_imu_vel, d.d_o_imu_vel, B * 3 * sizeof(double)},
+                    {ho->d_true_pos, d.d_true_pos, B * 3 * sizeof(double)}, {ho->d_true_b_vel, d.d_true_b_vel, B * 3 * sizeof(double)},
+                    {ho->d_contact_forces, d.d_contact_forces, B * 12 * sizeof(double)},
+                    {ho->d_joint_torques, d.d_joint_torques, B * 12 * sizeof(double)}});
+}
+
+extern "C" int qrw_sim_init(qrw_handle h, const double* d_q_init, int32_t q_ld, const qrw_sim_params* params, const qrw_sim_buffers* out,
+                            void* stream) {
+  QRW_ENTER(h, !d_q_init || !params || !out, "qrw_sim_init: null argument");
+  if (q_ld != 19 && q_ld != 12) return fail(-1, "qrw_sim_init: q_ld must be 19 (q19) or 12 (joints)");
+  if (const char* bad = sim_bad_params(params)) return fail(-1, (std::string("qrw_sim_init: ") + bad).c_str());
+  if (!sim_buffers_complete(out)) return fail(-1, "qrw_sim_init: null output buffer");
+  if (!h->sim_st) {
+    HIP_OK(h->sim_st.alloc((size_t)h->cfg.batch * qrw::kSimStItems), "qrw_sim_init: hipMalloc sim_st");
+    HIP_OK(h->sim_st.fill(0, (hipStream_t)stream), "qrw_sim_init: zero fill of sim_st");
+  }
+  h->sim_prm = *params;
+  qrw::SimArgs a = sim_common(h, 1, out);
+  a.q_init = d_q_init; a.q_ld = q_ld;
+  if (qrw::sim_launch(a, (hipStream_t)stream) != 0) return fail(-11, "qrw_sim_init: launch failed", hipGetLastError());
+  note_launch(h, kFamSim, (hipStream_t)stream);
+  h->sim_ready = true;
+  return 0;
+}
+
+extern "C" int qrw_sim_step(qrw_handle h, const double* d_P, const double* d_D, const double* d_q_des, const double* d_v_des,
+                            const double* d_tau_ff, int32_t cmd_ld, const double* d_f_ext, const qrw_sim_buffers* out, void* stream) {
+  QRW_ENTER(h, !h->sim_ready, "qrw_sim_step: simulator not initialised");
+  if (!d_P || !d_D || !d_q_des || !d_v_des || !d_tau_ff) return fail(-1, "qrw_sim_step: null input");
+  if (cmd_ld < 12) return fail(-1, "qrw_sim_step: cmd_ld must be >= 12");
+  if (!sim_buffers_complete(out)) return fail(-1, "qrw_sim_step: null output buffer");
+  qrw::SimArgs a = sim_common(h, 0, out);
+  a.P = d_P; a.D = d_D; a.q_des = d_q_des; a.v_des = d_v_des; a.tau_ff = d_tau_ff; a.cmd_ld = cmd_ld; a.f_ext = d_f_ext;
+  if (qrw::sim_launch(a, (hipStream_t)stream) != 0) return fail(-11, "qrw_sim_step: launch failed", hipGetLastError());
+  note_launch(h, kFamSim, (hipStream_t)stream);
+  return 0;
+}
+
+extern "C" int qrw_sim_init_host(qrw_handle h, const double* h_q_init, int32_t q_ld, const qrw_sim_params* params,
+                                 const qrw_sim_buffers* h_out) {
+  QRW_ENTER_HOST(h, !h_q_init || !params || !h_out, "qrw_sim_init_host: null argument");
+  if (q_ld != 19 && q_ld != 12) return fail(-1, "qrw_sim_init_host: q_ld must be 19 (q19) or 12 (joints)");
+  const size_t B = h->cfg.batch;
+  HIP_OK(wait_family(h, kFamSim), "qrw_sim_init_host: earlier simulator step of this handle");
+  if (!h->sim_out) {
+    HIP_OK(h->sim_out.alloc(B * kSimOutPerInstance), "qrw_sim_init_host: hipMalloc sim_out");
+    HIP_OK(h->sim_out.fill(0, h->host_stream), "qrw_sim_init_host: zero fill of sim_out");
+  }
+  Stager s(h);
+  const double* q = s.in(h_q_init, B * (size_t)q_ld);
+  if (!s.ok) return fail(-12, "qrw_sim_init_host: staging failed");
+  const qrw_sim_buffers own = sim_own_buffers(h);
+  if (const int rc = qrw_sim_init(h, q, q_ld, params, &own, (void*)h->host_stream)) return rc;
+  return sim_read_own(h, h_out, "qrw_sim_init_host");
+}
+
+extern "C" int qrw_sim_step_host(qrw_handle h, const double* h_P, const double* h_D, const double* h_q_des, const double* h_v_des,
+                                 const double* h_tau_ff, const double* h_f_ext, const qrw_sim_buffers* h_out) {
+  QRW_ENTER_HOST(h, !h->sim_ready || !h->sim_out, "qrw_sim_step_host: simulator not initialised with qrw_sim_init_host");
+  if (!h_P || !h_D || !h_q_des || !h_v_des || !h_tau_ff || !h_out) return fail(-1, "qrw_sim_step_host: null argument");
+  const size_t B = h->cfg.batch;
+  HIP_OK(wait_family(h, kFamSim), "qrw_sim_step_host: earlier simulator step of this handle");
+  Stager s(h);
+  const double *P = s.in(h_P, B * 12), *D = s.in(h_D, B * 12), *qd = s.in(h_q_des, B * 12), *vd = s.in(h_v_des, B * 12),
+               *tf = s.in(h_tau_ff, B * 12);
+  const double* fe = h_f_ext ? s.in(h_f_ext, B * 6) : nullptr;
+  if (!s.ok) return fail(-12, "qrw_sim_step_host: staging failed");
+  const qrw_sim_buffers own = sim_own_buffers(h);
+  if (const int rc = qrw_sim_step(h, P, D, qd, vd, tf, 12, fe, &own, (void*)h->host_stream)) return rc;
+  return sim_read_own(h, h_out, "qrw_sim_step_host");
+}
+
+extern "C" int qrw_sim_get_host(qrw_handle h, double* h_state) {
+  QRW_ENTER_HOST(h, !h_state, "qrw_sim_get_host: null argument");
+  if (!h->sim_ready) return fail(-1, "qrw_sim_get_host: simulator not initialised");
+  return read_back(h, kFamSim, "qrw_sim_get_host", {{h_state, h->sim_st.p, h->sim_st.bytes}});
+}
+
+extern "C" int qrw_sim_set_host(qrw_handle h, const double* h_state) {
+  QRW_ENTER_HOST(h, !h_state, "qrw_sim_set_host: null argument");
+  if (!h->sim_ready) return fail(-1, "qrw_sim_set_host: simulator not initialised");
+  HIP_OK(wait_family(h, kFamSim), "qrw_sim_set_host: earlier simulator step of this handle");
+  HIP_OK(h2d(h, h->sim_st.p, h_state, h->sim_st.bytes), "qrw_sim_set_host: H2D simulator state");
+  HIP_OK(host_done(h), "qrw_sim_set_host: H2D simulator state");
+  note_launch(h, kFamSim, h->host_stream);
   return 0;
 }
 

@@ -72,7 +72,7 @@ struct PinnedWord {
 
 // state families of a handle: which launches a getter has to wait for
 // (the controller-glue kernels write state no getter reads: their launches are not tracked)
-enum Family { kFamNone = -1, kFamMpc = 0, kFamWbc = 1, kFamPlan = 2, kFamEst = 3, kFamCount = 4 };
+enum Family { kFamNone = -1, kFamMpc = 0, kFamWbc = 1, kFamPlan = 2, kFamEst = 3, kFamSim = 4, kFamCount = 5 };
 
 }  // namespace qrw::host
 
@@ -116,6 +116,11 @@ struct qrw_handle_s {
   qrw_estimator_config ecfg;
   double est_alpha_v = 0.0, est_alpha_secu = 0.0;
   bool est_ready = false;
+  // rigid-body simulator: its state, its parameters, and the measurement buffers of the host-buffer entry points (allocated by
+  // qrw_sim_init_host: a frozen robot's rows keep their last finite values there, as in a caller's device buffers)
+  DevBuf<double> sim_st, sim_out;
+  qrw_sim_params sim_prm;
+  bool sim_ready = false;
   // staging for the host-buffer entry points
   DevBuf<double> stage;
   DevBuf<int32_t> stage_i;

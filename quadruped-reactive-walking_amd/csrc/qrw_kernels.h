@@ -209,4 +209,29 @@ struct EstimatorArgs {
   double* es;                                              // [kEstStItems][B]
 };
 int estimator_launch(const EstimatorArgs& a, hipStream_t stream);
+
+// ---- rigid-body simulator (sim_kernel.hip)
+// persistent state: ss[item][B] (item-major, as the estimator's)
+enum SimStateItem {
+  kSsQ = 0,       // q19: base position, quaternion xyzw, 12 joints (FL, FR, HL, HR)
+  kSsV = 19,      // v18: base linear / angular velocity in the base frame, joint velocities
+  kSsPrevImu = 37,  // prev_o_imuVel (3)
+  kSsTick = 40,
+  kSsStatus = 41,  // 0, or 1 once a tick's new state was not finite (the robot is frozen from then on)
+  kSimStItems = 42
+};
+struct SimArgs {
+  int B, mode;  // mode: 0 one tick, 1 init (state from q_init, first measurement), 2 forward dynamics of (fd_q, fd_v, fd_tau) only
+  int q_ld, cmd_ld, substeps;
+  double dt, kn, dn, mu, vs, foot_radius, base_height;
+  const double* q_init;                            // init: [B][q_ld], q_ld = 19 (q19) or 12 (joints; base at base_height, level)
+  const double *P, *D, *q_des, *v_des, *tau_ff;    // [B] rows of 12, cmd_ld doubles apart
+  const double* f_ext;                             // [B][6] world force and moment at the base origin, or null
+  double* ss;                                      // [kSimStItems][B]
+  double *q_mes, *v_mes, *quat, *ang_vel, *o_imu_vel, *lin_acc, *true_pos, *true_b_vel;  // [B][12] x2, [B][4], [B][3] x5
+  double *contact_forces, *joint_torques;          // [B][4][3] world, [B][12]
+  const double *fd_q, *fd_v, *fd_tau;              // mode 2: [B][19], [B][18], [B][12]
+  double* fd_a;                                    // mode 2: [B][18]
+};
+int sim_launch(const SimArgs& a, hipStream_t stream);
 }

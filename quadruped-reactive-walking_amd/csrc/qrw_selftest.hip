@@ -256,3 +256,35 @@ extern "C" int qrw_test_poke_aborted(qrw_handle h, int32_t parked_at) {
   }
   return 0;
 }
+
+// Tests only: the simulator's forward dynamics alone, for n states given in host buffers (no handle state is read or written).
+extern "C" int qrw_test_sim_forward_dynamics(qrw_handle h, int32_t n, const double* h_q19, const double* h_v18, const double* h_tau12,
+                                             const double* h_f_ext, const qrw_sim_params* params, double* h_a18, double* h_contact_forces) {
+  if (!h || n < 1 || !h_q19 || !h_v18 || !h_tau12 || !params || !h_a18 || !h_contact_forces)
+    return fail(-1, "qrw_test_sim_forward_dynamics: bad argument");
+  DeviceScope dev_scope__(h->cfg.device);
+  const size_t N = (size_t)n;
+  DevBuf<double> q, v, tau, fe, a18, cf;
+  HIP_OK(q.alloc(N * 19), "qrw_test_sim_forward_dynamics alloc");
+  HIP_OK(v.alloc(N * 18), "qrw_test_sim_forward_dynamics alloc");
+  HIP_OK(tau.alloc(N * 12), "qrw_test_sim_forward_dynamics alloc");
+  HIP_OK(a18.alloc(N * 18), "qrw_test_sim_forward_dynamics alloc");
+  HIP_OK(cf.alloc(N * 12), "qrw_test_sim_forward_dynamics alloc");
+  HIP_OK(hipMemcpy(q, h_q19, q.bytes, hipMemcpyHostToDevice), "qrw_test_sim_forward_dynamics H2D");
+  HIP_OK(hipMemcpy(v, h_v18, v.bytes, hipMemcpyHostToDevice), "qrw_test_sim_forward_dynamics H2D");
+  HIP_OK(hipMemcpy(tau, h_tau12, tau.bytes, hipMemcpyHostToDevice), "qrw_test_sim_forward_dynamics H2D");
+  if (h_f_ext) {
+    HIP_OK(fe.alloc(N * 6), "qrw_test_sim_forward_dynamics alloc");
+    HIP_OK(hipMemcpy(fe, h_f_ext, fe.bytes, hipMemcpyHostToDevice), "qrw_test_sim_forward_dynamics H2D");
+  }
+  qrw::SimArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = n; a.mode = 2; a.substeps = 1; a.dt = params->dt;
+  a.kn = params->kn; a.dn = params->dn; a.mu = params->mu; a.vs = params->vs; a.foot_radius = params->foot_radius;
+  a.fd_q = q; a.fd_v = v; a.fd_tau = tau; a.f_ext = h_f_ext ? fe.p : nullptr; a.fd_a = a18; a.contact_forces = cf;
+  if (qrw::sim_launch(a, h->host_stream) != 0) return fail(-11, "qrw_test_sim_forward_dynamics: launch failed", hipGetLastError());
+  HIP_OK(hipStreamSynchronize(h->host_stream), "qrw_test_sim_forward_dynamics");
+  HIP_OK(hipMemcpy(h_a18, a18, a18.bytes, hipMemcpyDeviceToHost), "qrw_test_sim_forward_dynamics D2H");
+  HIP_OK(hipMemcpy(h_contact_forces, cf, cf.bytes, hipMemcpyDeviceToHost), "qrw_test_sim_forward_dynamics D2H");
+  return 0;
+}

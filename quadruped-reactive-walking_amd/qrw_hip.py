@@ -38,6 +38,32 @@ ESTIMATOR_ITEMS = {"k_since_contact": (0, 4), "FK_lin_vel": (1, 3), "FK_xyz": (2
                    "close_from_contact": (9, 1), "offset_yaw_IMU": (10, 1), "k_log": (11, 1), "filt_lin_vel": (12, 3)}
 
 
+class _SimParams(C.Structure):
+    """qrw_sim_params (include/qrw_hip.h), field for field."""
+    _fields_ = [("dt", C.c_double), ("substeps", C.c_int32), ("kn", C.c_double), ("dn", C.c_double), ("mu", C.c_double),
+                ("vs", C.c_double), ("foot_radius", C.c_double), ("base_height", C.c_double)]
+
+
+SIM_DEFAULTS = dict(dt=0.002, substeps=8, kn=1e4, dn=60.0, mu=0.9, vs=0.01, foot_radius=0.0155, base_height=0.2596)
+# qrw_sim_buffers, field for field: name -> trailing shape
+SIM_OUTPUTS = (("q_mes", (12,)), ("v_mes", (12,)), ("quat", (4,)), ("ang_vel", (3,)), ("lin_acc", (3,)), ("o_imu_vel", (3,)),
+               ("true_pos", (3,)), ("true_b_vel", (3,)), ("contact_forces", (4, 3)), ("joint_torques", (12,)))
+SIM_STATE_ITEMS = 42  # q19, v18, prev_o_imuVel (3), tick, status
+
+
+class _SimBuffers(C.Structure):
+    _fields_ = [("d_" + n, C.c_void_p) for n, _ in SIM_OUTPUTS]
+
+
+def sim_params(**params):
+    unknown = set(params) - set(SIM_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown simulator parameters %s (%s)" % (sorted(unknown), ", ".join(SIM_DEFAULTS)))
+    p = dict(SIM_DEFAULTS, **params)
+    return _SimParams(float(p["dt"]), int(p["substeps"]), float(p["kn"]), float(p["dn"]), float(p["mu"]), float(p["vs"]),
+                      float(p["foot_radius"]), float(p["base_height"]))
+
+
 class _IterationBuffers(C.Structure):
     """qrw_iteration_buffers (include/qrw_hip.h), field for field."""
     _fields_ = ([(n, C.c_void_p) for n in ("d_joy_vref", "d_q_filt", "d_v_filt", "d_rpy", "d_v_secu", "d_code")]
@@ -100,6 +126,12 @@ SIGNATURES = {
     "qrw_estimator_step": (C.c_int, [_vp] + [_vp] * 13 + [_vp]),
     "qrw_estimator_step_host": (C.c_int, [_vp] + [_dp] * 13),
     "qrw_estimator_get_host": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _dp]),
+    "qrw_sim_init": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(_SimParams), C.POINTER(_SimBuffers), _vp]),
+    "qrw_sim_step": (C.c_int, [_vp] + [_vp] * 5 + [C.c_int32, _vp, C.POINTER(_SimBuffers), _vp]),
+    "qrw_sim_init_host": (C.c_int, [_vp, _dp, C.c_int32, C.POINTER(_SimParams), C.POINTER(_SimBuffers)]),
+    "qrw_sim_step_host": (C.c_int, [_vp] + [_dp] * 6 + [C.POINTER(_SimBuffers)]),
+    "qrw_sim_get_host": (C.c_int, [_vp, _dp]),
+    "qrw_sim_set_host": (C.c_int, [_vp, _dp]),
     "qrw_stream_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
     "qrw_stream_destroy": (C.c_int, [_vp]),
     "qrw_device_cu_count": (C.c_int, [C.c_int32, _ip]),
@@ -114,6 +146,7 @@ TEST_SIGNATURES = {
     "qrw_test_poison_probe": (C.c_int, [C.POINTER(C.c_uint32)]),
     "qrw_test_known_answer": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                        C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "qrw_test_sim_forward_dynamics": (C.c_int, [_vp, C.c_int32, _dp, _dp, _dp, _dp, C.POINTER(_SimParams), _dp, _dp]),
 }
 
 _lib = None
@@ -668,6 +701,89 @@ class Batch:
         out = np.empty(count)
         _check(self._lib.qrw_estimator_get_host(self._handle, which, int(b), count, _p(out)), "qrw_estimator_get_host")
         return out
+
+    # ------------------------------------------------ rigid-body simulator (csrc/sim_kernel.hip)
+    def sim_outputs(self):
+        """Zeroed device tensors for the outputs of a simulator tick, by the names of SIM_OUTPUTS."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        return {n: torch.zeros((self.B,) + shape, dtype=torch.float64, device=dev) for n, shape in SIM_OUTPUTS}
+
+    def _sim_buffers(self, out):
+        return _SimBuffers(*[self._dev(out[n], (self.B,) + shape).value for n, shape in SIM_OUTPUTS])
+
+    def sim_init(self, q_init, out, **params):
+        """qrw_sim_init: q_init (B,19) or (B,12) CUDA float64; out = sim_outputs().  Enqueues on the current stream."""
+        if q_init.dim() != 2 or q_init.shape[1] not in (12, 19):
+            raise QrwError("q_init must be (B,19) or (B,12)")
+        q_ld = int(q_init.shape[1])
+        prm, bufs = sim_params(**params), self._sim_buffers(out)
+        _check(self._lib.qrw_sim_init(self._handle, self._dev(q_init, (self.B, q_ld)), q_ld, C.byref(prm), C.byref(bufs),
+                                      self._stream()), "qrw_sim_init")
+
+    def sim_step(self, P, D, q_des, v_des, tau_ff, out, f_ext=None):
+        """qrw_sim_step: the five commands (B,12) CUDA float64 -- plain tensors, or the five planes of ONE contiguous (B,5,12)
+        result tensor (Controller.Result), which are read in place; f_ext (B,6) or None.  Enqueues on the current stream."""
+        cmd = (P, D, q_des, v_des, tau_ff)
+        if all(t.is_contiguous() for t in cmd):
+            ptrs, ld = [self._dev(t, (self.B, 12)) for t in cmd], 12
+        else:
+            base, ld = P.data_ptr(), 60
+            if [tuple(t.shape) for t in cmd] != [(self.B, 12)] * 5 or any(t.stride() != (60, 1) or t.dtype != P.dtype for t in cmd) or \
+                    [t.data_ptr() - base for t in cmd] != [96 * i for i in range(5)] or not P.is_cuda or P.element_size() != 8:
+                raise QrwError("the commands must be five contiguous (B,12) tensors or the planes of one (B,5,12) result tensor")
+            ptrs = [_vp(t.data_ptr()) for t in cmd]
+        bufs = self._sim_buffers(out)
+        fe = _vp(0) if f_ext is None else self._dev(f_ext, (self.B, 6))
+        _check(self._lib.qrw_sim_step(self._handle, *ptrs, ld, fe, C.byref(bufs), self._stream()), "qrw_sim_step")
+        return out
+
+    def _sim_host_out(self):
+        o = {n: np.zeros((self.B,) + shape) for n, shape in SIM_OUTPUTS}
+        return o, _SimBuffers(*[o[n].ctypes.data for n, _ in SIM_OUTPUTS])
+
+    def sim_init_host(self, q_init, **params):
+        """qrw_sim_init_host with numpy arrays; returns the dict of the first measurement."""
+        q_init = np.ascontiguousarray(np.asarray(q_init, dtype=np.float64)).reshape(self.B, -1)
+        o, bufs = self._sim_host_out()
+        prm = sim_params(**params)
+        _check(self._lib.qrw_sim_init_host(self._handle, _p(q_init), int(q_init.shape[1]), C.byref(prm), C.byref(bufs)),
+               "qrw_sim_init_host")
+        return o
+
+    def sim_step_host(self, P, D, q_des, v_des, tau_ff, f_ext=None):
+        """qrw_sim_step_host with numpy arrays (what the single-robot drop-in PyBulletSimulator.py uses)."""
+        a = [_h(np.broadcast_to(np.asarray(x, dtype=np.float64), (self.B, 12)), (self.B, 12)) for x in (P, D, q_des, v_des, tau_ff)]
+        fe = None if f_ext is None else _h(f_ext, (self.B, 6))
+        o, bufs = self._sim_host_out()
+        _check(self._lib.qrw_sim_step_host(self._handle, *[_p(x) for x in a], _p(fe), C.byref(bufs)), "qrw_sim_step_host")
+        return o
+
+    def sim_state(self):
+        """The whole simulator state as dict(q (B,19), v (B,18), prev_o_imuVel (B,3), tick (B,), status (B,)), numpy."""
+        st = np.empty((SIM_STATE_ITEMS, self.B))
+        _check(self._lib.qrw_sim_get_host(self._handle, _p(st)), "qrw_sim_get_host")
+        st = np.ascontiguousarray(st.T)
+        return dict(q=st[:, :19].copy(), v=st[:, 19:37].copy(), prev_o_imuVel=st[:, 37:40].copy(), tick=st[:, 40].astype(np.int64),
+                    status=st[:, 41].astype(np.int64))
+
+    def sim_set_state(self, q, v, prev_o_imuVel, tick=0, status=0):
+        st = np.empty((self.B, SIM_STATE_ITEMS))
+        st[:, :19], st[:, 19:37], st[:, 37:40] = _h(q, (self.B, 19)), _h(v, (self.B, 18)), _h(prev_o_imuVel, (self.B, 3))
+        st[:, 40], st[:, 41] = tick, status
+        _check(self._lib.qrw_sim_set_host(self._handle, _p(np.ascontiguousarray(st.T))), "qrw_sim_set_host")
+
+    def test_sim_forward_dynamics(self, q19, v18, tau12, f_ext=None, **params):
+        """Tests only (qrw_test_sim_forward_dynamics): a18 (n,18) and the contact forces (n,4,3) of n states."""
+        q19 = np.ascontiguousarray(np.asarray(q19, dtype=np.float64)).reshape(-1, 19)
+        n = q19.shape[0]
+        a, f = np.empty((n, 18)), np.empty((n, 4, 3))
+        prm = sim_params(**params)
+        _check(self._lib.qrw_test_sim_forward_dynamics(self._handle, n, _p(q19), _p(_h(v18, (n, 18))), _p(_h(tau12, (n, 12))),
+                                                       _p(None if f_ext is None else _h(f_ext, (n, 6))), C.byref(prm), _p(a), _p(f)),
+               "qrw_test_sim_forward_dynamics")
+        return a, f
 
     # ------------------------------------------------ getters / diagnostics
     def mpc_gait(self, b=0):
