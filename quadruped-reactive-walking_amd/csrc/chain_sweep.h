@@ -100,6 +100,8 @@ __device__ __forceinline__ double swap_rows16(double v) {
 // TWO consecutive steps -- lanes 0..31 those of step 2p+1, lanes 32..63 those of step 2p+2 -- and the running vector
 // changes halves between the steps (two v_permlane32_swap): half the LDS instructions and half the LDS bandwidth of
 // the one-step form, the same 12 FMAs per step in the same order (bit-identical results).
+// This form, with an exchange after every step, remains for compile-time chain lengths that are even but no multiple of 4;
+// the solver's own N = 16 and N = 32 take the 2 + 2 half order further down (chain_forward_quad / chain_backward_quad).
 template <int NC>
 __device__ __forceinline__ void chain_forward_paired(const double* sN, double* sX, double* sDump, int lane) {
   constexpr int N = NC, m = N >> 1, LA = m, LB = N - 1 - m, NP = LA / 2;
@@ -209,10 +211,132 @@ __device__ __forceinline__ void chain_backward_paired(const double* sN, double* 
   }
 }
 
+// Paired sweeps in the 2 + 2 half order (compile-time N with a chain length that is a multiple of 4: N = 16, 32).  The
+// exchange after every step is the costly part of the form above: an s_nop and two v_permlane32_swap on the dependent
+// chain, a step with one takes ~177 clocks against 66 for the 12 FMAs alone.  The same reads serve an order that needs
+// half of them: the steps visit the halves as lower, lower, upper, upper.  Buffer X holds step 4q+1 in lanes 0..31 and
+// step 4q+3 in lanes 32..63, buffer Y steps 4q+2 / 4q+4 (each half reads slots 0 / +2 instead of 0 / +1), and the
+// running vector changes halves only after steps 4q+2 and 4q+4: 3 + 3 exchanges per iteration at N = 16 instead of
+// 7 + 7, 7 + 7 at N = 32 instead of 15 + 15.  Same LDS instructions and bytes, same operand registers, the same 12
+// FMAs per step in the same order (bit-identical results).  A buffer is free after its upper-half use and is reloaded
+// right there, i.e. one step and one exchange (~180 clocks) ahead of its next use instead of one pair (~350).
+// Stores: a step without an exchange is stored by the lanes of the half it was computed in, a step with one after it
+// (in place, as above) by the other half; everybody else stores to sDump, at the same offsets as above.
+template <int NC>
+__device__ __forceinline__ void chain_forward_quad(const double* sN, double* sX, double* sDump, int lane) {
+  constexpr int N = NC, m = N >> 1, LA = m, LB = N - 1 - m, NQ = LA / 4;
+  static_assert(LA % 4 == 0 && LB == LA - 1, "the 2 + 2 half order needs a chain length that is a multiple of 4");
+  const int i = ((lane & 15) < 12) ? (lane & 15) : 11;
+  const int h = lane >> 5;
+  const bool rw = (lane & 16) != 0;
+  const bool own = (lane & 15) < 12;
+  const double* pm = sN + (rw ? m * kSlot + chain_gap(m) : 0) + 2 * h * kSlot + i;  // X of quad q: + 4q*kSlot + c*kCol, Y: + kSlot more
+  double* px = sX + (rw ? (m + 1) * 12 : 0) + i;           // step t: + t*12
+  const double* pr = px + 2 * h * 12;                      // rhs, X of quad q: + (4q+1)*12, Y: + (4q+2)*12
+  double* dump = sDump + i;
+  double* ps_lo = (own && h == 0) ? px : dump;             // steps 4q+1 (not exchanged) and 4q+4 (exchanged), both chains
+  double* ps_hi = (own && h == 1) ? px : dump;             // steps 4q+2 (exchanged) and 4q+3 < LB (not exchanged), both chains
+  double* ps_hiA = (own && h == 1 && !rw) ? px : dump;     // step LB (= 4q+3 of the last quad): chain A only
+  double x = px[0], pB = 0.0;
+  ChainOp bX, bY;
+  auto fetch = [&](ChainOp& b, int s) {  // s: slot (= step - 1) of the lower half
+    const double* q = pm + s * kSlot;
+#pragma unroll
+    for (int c = 0; c < 12; c++) b.m[c] = __hip_atomic_load(q + c * kCol, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    b.r = pr[(s + 1) * 12];
+  };
+  fetch(bX, 0);
+  fetch(bY, 1);
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const int t = 4 * q;
+    __builtin_amdgcn_sched_barrier(0);
+    x = dpp_step12(bX.r, x, bX.m);  // step t+1, lanes 0..31
+    ps_lo[(t + 1) * 12] = x;
+    x = dpp_step12(bY.r, x, bY.m);  // step t+2, lanes 0..31
+    x = swap_halves(x);             // now in lanes 32..63
+    ps_hi[(t + 2) * 12] = x;
+    x = dpp_step12(bX.r, x, bX.m);  // step t+3, lanes 32..63
+    if (t + 3 == LB) pB = x;
+    (t + 3 < LB ? ps_hi : ps_hiA)[(t + 3) * 12] = x;
+    if (q + 1 < NQ) fetch(bX, t + 4);
+    __builtin_amdgcn_sched_barrier(0);
+    x = dpp_step12(bY.r, x, bY.m);  // step t+4, lanes 32..63
+    if (q + 1 < NQ) {
+      x = swap_halves(x);           // now in lanes 0..31
+      ps_lo[(t + 4) * 12] = x;
+      fetch(bY, t + 5);
+    }
+  }
+  // root: chain A's last step (LA, the fourth of the last quad) sits in lanes 32..43 (row 2), chain B's contribution
+  // (step LB, the third, computed in the upper half) in lanes 48..59 (row 3): a row exchange instead of an LDS round trip
+  x += swap_rows16(pB);
+  if (lane >= 32 && lane < 44) sX[m * 12 + i] = x;
+}
+template <int NC>
+__device__ __forceinline__ void chain_backward_quad(const double* sN, double* sX, double* sDump, int lane) {
+  constexpr int N = NC, m = N >> 1, LA = m, LB = N - 1 - m, NQ = LA / 4;
+  static_assert(LA % 4 == 0 && LB == LA - 1, "the 2 + 2 half order needs a chain length that is a multiple of 4");
+  const int i = ((lane & 15) < 12) ? (lane & 15) : 11;
+  const int h = lane >> 5;
+  const bool rw = (lane & 16) != 0;
+  const bool own = (lane & 15) < 12;
+  const int ib = chain_row_t(lane);
+  // step t reads slot (top - t) and vector position (top - t); the upper half is two steps further down
+  const double* pm = sN + ((rw ? (N - 1) : m) - LA - 2 * h) * kSlot + (rw ? chain_gap(m) : 0) + ib * kCol;  // X of quad q: + (LA-4q-1)*kSlot + c, Y: one slot less
+  double* px = sX + ((rw ? N : m) - LA) * 12 + i;                                                           // step t: + (LA-t)*12
+  const double* pr = px - 2 * h * 12;                                                                       // rhs, X of quad q: + (LA-4q-1)*12, Y: 12 less
+  double* dump = sDump + i;
+  double* ps_lo = (own && h == 0) ? px : dump;             // steps 4q+1 (not exchanged) and 4q+4 < LA (exchanged), both chains
+  double* ps_hi = (own && h == 1) ? px : dump;             // steps 4q+2 (exchanged) and 4q+3 <= LB (not exchanged), both chains
+  double* ps_lastA = (own && h == 1 && !rw) ? px : dump;   // step LA (not exchanged): chain A only
+  double x = sX[m * 12 + i];
+  ChainOp bX, bY;
+  auto fetch = [&](ChainOp& b, int t) {  // t: step of the lower half (the upper half fetches step t + 2)
+    const qrw_d2* q = reinterpret_cast<const qrw_d2*>(pm + (LA - t) * kSlot);
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      const qrw_d2 v = q[c];
+      b.m[2 * c] = v.x;
+      b.m[2 * c + 1] = v.y;
+    }
+    b.r = pr[(LA - t) * 12];
+  };
+  fetch(bX, 1);
+  fetch(bY, 2);
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const int t = 4 * q;
+    __builtin_amdgcn_sched_barrier(0);
+    x = dpp_step12(bX.r, x, bX.m);  // step t+1, lanes 0..31
+    ps_lo[(LA - t - 1) * 12] = x;
+    x = dpp_step12(bY.r, x, bY.m);  // step t+2, lanes 0..31
+    x = swap_halves(x);
+    ps_hi[(LA - t - 2) * 12] = x;
+    x = dpp_step12(bX.r, x, bX.m);  // step t+3 <= LB, lanes 32..63
+    ps_hi[(LA - t - 3) * 12] = x;
+    if (q + 1 < NQ) fetch(bX, t + 5);
+    __builtin_amdgcn_sched_barrier(0);
+    x = dpp_step12(bY.r, x, bY.m);  // step t+4, lanes 32..63
+    if (q + 1 < NQ) {
+      x = swap_halves(x);
+      ps_lo[(LA - t - 4) * 12] = x;  // t+4 < LA = LB + 1: both chains
+      fetch(bY, t + 6);
+    } else {
+      ps_lastA[0] = x;
+    }
+  }
+}
+
 // sDump: (NC/2 + 2) * 12 doubles of LDS that absorb the stores of lanes / steps that must not write (cheaper than
-// switching EXEC around every store: a lone wavefront pays full issue time for each scalar instruction).
+// switching EXEC around every store: a lone wavefront pays full issue time for each scalar instruction).  The sweeps
+// above store step t at offset t*12 (forward, t < NC/2) or (NC/2 - t)*12 (backward, t >= 1), whichever half stores it.
 template <int NC>
 __device__ __forceinline__ void chain_forward(const double* sN, double* sX, double* sDump, int Nrt, int lane) {
+  if constexpr (NC > 0 && (NC / 2) % 4 == 0) {
+    chain_forward_quad<NC>(sN, sX, sDump, lane);
+    return;
+  }
   if constexpr (NC > 0 && (NC / 2) % 2 == 0) {
     chain_forward_paired<NC>(sN, sX, sDump, lane);
     return;
@@ -265,6 +389,10 @@ __device__ __forceinline__ void chain_forward(const double* sN, double* sX, doub
 // Transposed reads of the same slots (row i of M' is contiguous: 6 ds_read_b128).
 template <int NC>
 __device__ __forceinline__ void chain_backward(const double* sN, double* sX, double* sDump, int Nrt, int lane) {
+  if constexpr (NC > 0 && (NC / 2) % 4 == 0) {
+    chain_backward_quad<NC>(sN, sX, sDump, lane);
+    return;
+  }
   if constexpr (NC > 0 && (NC / 2) % 2 == 0) {
     chain_backward_paired<NC>(sN, sX, sDump, lane);
     return;

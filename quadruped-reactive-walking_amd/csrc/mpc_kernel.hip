@@ -1812,28 +1812,32 @@ int mpc_sequence_launch(const MpcArgs& a, hipStream_t stream) {
 // ---- self-test of what the solver's linear algebra relies on: v_fmac_f64_dpp row_newbcast semantics, the twisted
 // sweeps of chain_sweep.h in the production LDS layout and the in-register Gauss-Jordan inverse -------------------------
 namespace qrw {
+// NC = 16 also inverts two 12x12 matrices; NC = 32 (a second kernel: its chain matrices alone are 42 KB of LDS) runs the sweeps only
+template <int NC>
 __global__ void sweeps_selftest_kernel(const double* M, const double* r, const double* G, double* out, double* ginv) {
-  __shared__ __attribute__((aligned(16))) double sN[chain_lds_doubles(16, 8)];
-  __shared__ double sX[18 * 12];
-  __shared__ double sDump[10 * 12];
+  __shared__ __attribute__((aligned(16))) double sN[chain_lds_doubles(NC, NC / 2)];
+  __shared__ double sX[(NC + 2) * 12];
+  __shared__ double sDump[(NC / 2 + 2) * 12];
   const int lane = threadIdx.x;
-  for (int e = lane; e < chain_lds_doubles(16, 8); e += 64) sN[e] = M[e];
-  for (int e = lane; e < 18 * 12; e += 64) sX[e] = r[e];
+  for (int e = lane; e < chain_lds_doubles(NC, NC / 2); e += 64) sN[e] = M[e];
+  for (int e = lane; e < (NC + 2) * 12; e += 64) sX[e] = r[e];
   __syncthreads();
-  chain_forward<16>(sN, sX, sDump, 16, lane);
+  chain_forward<NC>(sN, sX, sDump, NC, lane);
   __syncthreads();
-  chain_backward<16>(sN, sX, sDump, 16, lane);
+  chain_backward<NC>(sN, sX, sDump, NC, lane);
   __syncthreads();
-  for (int e = lane; e < 18 * 12; e += 64) out[e] = sX[e];
-  // two 12x12 inverses at once (DPP rows 0 and 1), rows 2-3 shadow them
-  const int i = ((lane & 15) < 12) ? (lane & 15) : 11, which = (lane >> 4) & 1;
-  double m[12];
+  for (int e = lane; e < (NC + 2) * 12; e += 64) out[e] = sX[e];
+  if constexpr (NC == 16) {
+    // two 12x12 inverses at once (DPP rows 0 and 1), rows 2-3 shadow them
+    const int i = ((lane & 15) < 12) ? (lane & 15) : 11, which = (lane >> 4) & 1;
+    double m[12];
 #pragma unroll
-  for (int c = 0; c < 12; c++) m[c] = G[which * 144 + i * 12 + c];
-  gj_invert12(m, i);
-  if (lane < 32 && (lane & 15) < 12)
+    for (int c = 0; c < 12; c++) m[c] = G[which * 144 + i * 12 + c];
+    gj_invert12(m, i);
+    if (lane < 32 && (lane & 15) < 12)
 #pragma unroll
-    for (int c = 0; c < 12; c++) ginv[which * 144 + i * 12 + c] = m[c];
+      for (int c = 0; c < 12; c++) ginv[which * 144 + i * 12 + c] = m[c];
+  }
 }
 
 namespace {
@@ -1852,14 +1856,29 @@ struct SelfTestStream {
 };
 }  // namespace
 
+template <int N>
+static int sweeps_selftest_n(double* max_err);
+
+// both compile-time horizons of the solver; the larger of the two errors
 int sweeps_selftest(double* max_err) {
-  constexpr int N = 16, m = N / 2;
-  std::vector<double> hMv(chain_lds_doubles(16, 8), 0.0), hrv(18 * 12), houtv(18 * 12), hGv(288), hGiv(288);
+  double e16 = 0.0, e32 = 0.0;
+  const int rc16 = sweeps_selftest_n<16>(&e16);
+  const int rc32 = (rc16 < 0) ? rc16 : sweeps_selftest_n<32>(&e32);
+  if (max_err) *max_err = fmax(e16, e32);
+  if (rc16 < 0 || rc32 < 0) return rc16 < 0 ? rc16 : rc32;
+  return (rc16 || rc32) ? 1 : 0;
+}
+
+// the sweeps at compile-time horizon N against a host evaluation of the same recursions; N = 16 adds the two inverses
+template <int N>
+static int sweeps_selftest_n(double* max_err) {
+  constexpr int m = N / 2;
+  std::vector<double> hMv(chain_lds_doubles(N, m), 0.0), hrv((N + 2) * 12), houtv((N + 2) * 12), hGv(288), hGiv(288);
   double *hM = hMv.data(), *hr = hrv.data(), *hout = houtv.data(), *hG = hGv.data(), *hGi = hGiv.data();
   for (int s = 0; s < N - 1; s++)
     for (int i = 0; i < 12; i++)
       for (int c = 0; c < 12; c++) hM[chain_slot(s, m) + c * kCol + i] = 0.25 * sin(0.37 * (s * 144 + i * 12 + c) + 1.0);
-  for (int e = 0; e < 18 * 12; e++) hr[e] = 0.0;
+  for (int e = 0; e < (N + 2) * 12; e++) hr[e] = 0.0;
   for (int k = 0; k < N; k++)
     for (int i = 0; i < 12; i++) hr[chain_pos(k, m, N) * 12 + i] = cos(0.11 * (k * 12 + i));
   for (int w = 0; w < 2; w++)  // diagonally dominant test matrices
@@ -1881,13 +1900,13 @@ int sweeps_selftest(double* max_err) {
   if (!bM.alloc(nM) || !br.alloc(nr) || !bG.alloc(nG) || !bout.alloc(nr) || !bGi.alloc(nG) || !st.create()) return -1;
   hipMemcpyAsync(bM.p, hM, nM, hipMemcpyHostToDevice, st.s); hipMemcpyAsync(br.p, hr, nr, hipMemcpyHostToDevice, st.s);
   hipMemcpyAsync(bG.p, hG, nG, hipMemcpyHostToDevice, st.s);
-  hipLaunchKernelGGL(sweeps_selftest_kernel, dim3(1), dim3(64), 0, st.s, bM.as<double>(), br.as<double>(), bG.as<double>(), bout.as<double>(),
+  hipLaunchKernelGGL(sweeps_selftest_kernel<N>, dim3(1), dim3(64), 0, st.s, bM.as<double>(), br.as<double>(), bG.as<double>(), bout.as<double>(),
                      bGi.as<double>());
   hipMemcpyAsync(hout, bout.p, nr, hipMemcpyDeviceToHost, st.s); hipMemcpyAsync(hGi, bGi.p, nG, hipMemcpyDeviceToHost, st.s);
   if (hipStreamSynchronize(st.s) != hipSuccess) return -2;
   double me = 0.0;
   for (int k = 0; k < N; k++) for (int i = 0; i < 12; i++) me = fmax(me, fabs(hout[chain_pos(k, m, N) * 12 + i] - u[k][i]) / 8.0);
-  for (int w = 0; w < 2; w++)  // G * G^-1 = I
+  for (int w = 0; w < (N == 16 ? 2 : 0); w++)  // G * G^-1 = I
     for (int i = 0; i < 12; i++)
       for (int c = 0; c < 12; c++) {
         double s = 0.0;
