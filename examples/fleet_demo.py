@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A fleet of Solo12 robots stepped by the device-resident control loop, paced at the reference's 2 ms (src/config_solo12.yaml:6).
 
-    python examples/fleet_demo.py [robots] [seconds] [sync|async|auto] [--sensors | --sim] [--vx=V]
+    python examples/fleet_demo.py [robots] [seconds] [sync|async|auto] [--sensors | --sim] [--kalman] [--vx=V]
 
 `Controller_batch` mirrors `Controller.compute` of the reference (scripts/Controller.py:200-326) for B robots: the estimator's
 outputs go in (reference velocity, filtered q / v, roll-pitch, joint velocities), the PD targets and feed-forward torques come out;
@@ -11,8 +11,10 @@ With --sensors the estimator runs on the device too (Controller_batch(..., estim
 robot delivers -- IMU acceleration, gyro, IMU orientation, encoder angles and velocities, here synthetic (synth.SyntheticSensors).
 With --sim the loop is closed: a simulated robot per controller (Simulator.Simulator_batch: forward dynamics with penalty contact on
 a flat plane, one more kernel per tick) takes the PD targets and torques and delivers the next readings; at the end the robots
-without an error flag and without a simulator status are counted and the distance they covered is printed.  --vx=V gives every
-robot the forward reference speed V and no yaw rate (default: 0 to 0.4 m/s and -0.3 to 0.3 rad/s, drawn per robot)."""
+without an error flag and without a simulator status are counted and the distance they covered is printed, next to the distance
+the estimator reads.  --kalman (implies --sensors unless --sim is given) runs the estimator with the reference's Kalman filter
+(KFilterBis, kf_enabled=True) instead of its complementary filters.  --vx=V gives every robot the forward reference speed V and
+no yaw rate (default: 0 to 0.4 m/s and -0.3 to 0.3 rad/s, drawn per robot)."""
 import os
 import sys
 import time
@@ -27,13 +29,14 @@ from Controller import Controller_batch  # noqa: E402
 from Simulator import Simulator_batch  # noqa: E402
 
 sim_on = "--sim" in sys.argv
-sensors = "--sensors" in sys.argv and not sim_on
+kalman = "--kalman" in sys.argv
+sensors = ("--sensors" in sys.argv or kalman) and not sim_on
 vx = [float(a[5:]) for a in sys.argv if a.startswith("--vx=")]
-argv = [a for a in sys.argv if a not in ("--sensors", "--sim") and not a.startswith("--vx=")]
+argv = [a for a in sys.argv if a not in ("--sensors", "--sim", "--kalman") and not a.startswith("--vx=")]
 B = int(argv[1]) if len(argv) > 1 else 1024
 seconds = float(argv[2]) if len(argv) > 2 else 1.0
 mode = argv[3] if len(argv) > 3 else "sync"
-est = dict(h_init=0.22294615) if (sensors or sim_on) else None  # (scripts/Estimator.py:245)
+est = dict(h_init=0.22294615, kalman=kalman) if (sensors or sim_on) else None  # (scripts/Estimator.py:245)
 dev = torch.device("cuda", 0)
 q_init = np.array([0.0, 0.7, -1.4, -0.0, 0.7, -1.4, 0.0, -0.7, +1.4, -0.0, -0.7, +1.4])  # scripts/main_solo12_control.py:120
 
@@ -88,18 +91,21 @@ with torch.cuda.stream(torch.cuda.Stream(dev)):  # (keep the caller's work off t
             st, flags = sim.state(), ctl.error_flag.cpu().numpy()
             good = (flags == 0) & (st["status"] == 0)
             fell = int((st["q"][good, 2] < 0.12).sum())
+            read_x = ctl.q_filt[:, 0].cpu().numpy()  # the estimator's base position against the simulator's
             sim_line = ("; closed loop: %d of %d robots end with error_flag 0 and simulator status 0 (error flags set %d %s, frozen %d); of those, "
                         "%d have the base below 0.12 m; base height median %.3f m, distance covered in x median %.3f m (min %.3f, max %.3f) in "
-                        "%.2f s at reference speeds %.2f..%.2f m/s"
+                        "%.2f s at reference speeds %.2f..%.2f m/s; the estimator (%s) reads median %.3f m in x, %.3f m base height"
                         % (int(good.sum()), B, int((flags != 0).sum()), dict(zip(*[x.tolist() for x in np.unique(flags, return_counts=True)])),
                            int((st["status"] != 0).sum()), fell,
                            float(np.median(st["q"][good, 2])) if good.any() else float("nan"),
                            *(([float(f(st["q"][good, 0])) for f in (np.median, np.min, np.max)]) if good.any() else [float("nan")] * 3),
-                           0.002 * (k + 1), v[:, 0].min(), v[:, 0].max()))
+                           0.002 * (k + 1), v[:, 0].min(), v[:, 0].max(), "Kalman filter" if kalman else "complementary filters",
+                           float(np.median(read_x[good])) if good.any() else float("nan"),
+                           float(np.median(ctl.q_filt[:, 2].cpu().numpy()[good])) if good.any() else float("nan")))
     ctl.stop_parallel_loop()
 lat = np.array(lat)
 warm = lat[20:]  # the first two MPC solves start cold (QP set-up, ~1 000 ADMM iterations): like the reference's first iterations
 print("%d robots, %s mode%s, %d ticks paced at 2 ms: tick latency median %.3f ms, worst %.3f ms after the first 20 ticks (%d ticks over the slot; "
       "cold start: %.3f ms); largest |tau_ff| %.2f N m; robots in security stop %d%s"
-      % (B, mode, ", simulator in the loop" if sim_on else ", sensors in" if sensors else "", len(lat), np.median(lat), warm.max(),
+      % (B, mode, (", simulator in the loop" if sim_on else ", sensors in" if sensors else "") + (", Kalman estimator" if kalman else ""), len(lat), np.median(lat), warm.max(),
          int((warm > 2.0).sum()), lat[:20].max(), tau, stopped, sim_line if sim_on else ""))

@@ -313,21 +313,43 @@ int qrw_iteration_bind(qrw_handle h, const qrw_iteration_buffers *buffers);
 int qrw_iteration_step(qrw_handle h, int32_t k, const double *d_x_f_mpc, void *stream);
 
 /* ---------------- state estimator: sensors in, filtered state out ----------------
- * The stage of Controller.compute before everything above (scripts/Controller.py:213): Estimator.run_filter with the
- * complementary filters (scripts/Estimator.py:466-629, kf_enabled = False as scripts/Controller.py:110-111 builds it), batched,
- * with its per-instance state (contact counters, the two filters, yaw offset, call counter) in the handle.  Its outputs are the
- * d_q_filt / d_v_filt / d_rpy / d_v_secu operands of qrw_controller_update_state, qrw_control_pre and qrw_iteration_bind: a
- * sensors-in iteration is qrw_estimator_step writing into those buffers, followed by qrw_iteration_step or qrw_control_pre on the
- * same stream.  Not provided: the Kalman variant (KFilter / KFilterBis), the logging arrays, plot_graphs.  One departure: the
- * scan for `remaining_steps` (:476-479) stops at N_gait where the reference raises IndexError (every row equal to row 0). */
+ * The stage of Controller.compute before everything above (scripts/Controller.py:213): Estimator.run_filter
+ * (scripts/Estimator.py:466-629), batched, with its per-instance state (contact counters, the filters, yaw offset, call counter)
+ * in the handle.  Both of the reference's filters for base position and velocity are provided, chosen by how the handle's
+ * estimator was last initialised: the cascade of complementary filters (qrw_estimator_init: kf_enabled = False, as
+ * scripts/Controller.py:110-111 builds it) and the Kalman filter over base position, base velocity and the four foot positions
+ * (qrw_estimator_init_kalman: KFilterBis, kf_enabled = True, :88-181 and :555-580).  Everything else of run_filter is common to
+ * the two.  The outputs are the d_q_filt / d_v_filt / d_rpy / d_v_secu operands of qrw_controller_update_state, qrw_control_pre
+ * and qrw_iteration_bind: a sensors-in iteration is qrw_estimator_step writing into those buffers, followed by
+ * qrw_iteration_step or qrw_control_pre on the same stream.  Not provided: KFilter (the 6-state class that Estimator never
+ * constructs), the logging arrays, plot_graphs.  One departure: the scan for `remaining_steps` (:476-479) stops at N_gait where
+ * the reference raises IndexError (every row equal to row 0). */
 typedef struct {
   double h_init;   /* initial base height: FK_xyz[2] and the position filter's low-pass state (scripts/Estimator.py:279-283) */
   int32_t perfect; /* perfectEstimator (:595-596, :601-602): base height and base-frame velocity taken from the true inputs   */
 } qrw_estimator_config;
 
-/* Replaces Estimator.__init__ (scripts/Estimator.py:245-342); dt is the handle's dt_wbc.  Resets the state: calling it again
- * re-initialises (the yaw offset is latched again by the next two steps). */
+/* Replaces Estimator.__init__ (scripts/Estimator.py:245-342) with kf_enabled = False; dt is the handle's dt_wbc.  Resets the
+ * state: calling it again re-initialises (the yaw offset is latched again by the next two steps), and switches a handle that
+ * was in Kalman mode back to the complementary filters: after it the handle's estimator is that of a fresh handle. */
 int qrw_estimator_init(qrw_handle h, const qrw_estimator_config *cfg, void *stream);
+
+/* The tuning values of the Kalman filter (scripts/Estimator.py:133-137; the reference's values: 0.1, 1.0, 0.1, 0.1, 30). */
+typedef struct {
+  double sigma_kin; /* kinematic measurement noise: R = sigma_kin^2 / trust on a foot's three rows                        */
+  double sigma_h;   /* foot height measurement noise: R = sigma_h^2 / trust on row 12 + foot                              */
+  double sigma_a;   /* acceleration noise: Q = sigma_a^2 dt^2 on the velocity states                                      */
+  double sigma_dp;  /* foot slip: Q = sigma_dp^2 (1 + exp(gamma (0.5 - trust))) dt^2 on a foot's states                   */
+  double gamma;     /* trust = 1 for a foot in stance, 0.01 in swing                                                      */
+} qrw_kalman_config;
+
+/* The same with kf_enabled = True: resets the shared state exactly as qrw_estimator_init does (except that the base height
+ * goes into X[2], not into the position filter, :282-285), sets X = 0 but X[2] = h_init and P = I (:121), and switches the
+ * handle's estimator to the Kalman filter; qrw_estimator_step / _step_host then run that.  kcfg NULL = the reference's values;
+ * the sigmas must be > 0 and finite, gamma finite.  The first call on a handle allocates the filter's state (142 doubles per
+ * instance: X, the three per-axis 6x6 blocks of P, the last Z), which stays with the handle until qrw_destroy and which
+ * qrw_state_bytes counts from then on; a handle that never calls it allocates nothing for it. */
+int qrw_estimator_init_kalman(qrw_handle h, const qrw_estimator_config *cfg, const qrw_kalman_config *kcfg, void *stream);
 
 /* Replaces Estimator.run_filter(k, gait, device, goals) (scripts/Estimator.py:466-629).  Only enqueues: no allocation, no
  * synchronisation.
@@ -352,6 +374,11 @@ int qrw_estimator_step_host(qrw_handle h, const double *h_lin_acc, const double 
  * 3 xyz_mean_feet (3), 4 / 5 filter_xyz_vel HP_x / LP_x (3), 6 / 7 filter_xyz_pos HP_x / LP_x (3), 8 alpha, 9 close_from_contact,
  * 10 offset_yaw_IMU, 11 k_log, 12 filt_lin_vel (3). */
 int qrw_estimator_get_host(qrw_handle h, int32_t which, int32_t b, int32_t count, double *h_out);
+/* ... of the Kalman filter's: which = 0 X (18), 1 P (324: row-major 18 x 18, assembled from the per-axis blocks, exact zeros
+ * between the axes), 2 Z (16, the last measurement).  -1 "not in Kalman mode" unless the estimator was last initialised by
+ * qrw_estimator_init_kalman.  (The items of qrw_estimator_get_host stay available; the complementary filters' halves keep
+ * their initial values in Kalman mode, as in the reference.) */
+int qrw_estimator_kalman_get_host(qrw_handle h, int32_t which, int32_t b, int32_t count, double *h_out);
 
 /* ---------------- rigid-body simulator: torques in, sensor readings out ----------------
  * What closes the loop around the controller: per instance one Solo12 on a flat plane, stepped on the device.  One tick is the

@@ -54,6 +54,23 @@ def auto_groups(batch, groups=None, multiprocessing=False):
     return int(groups) if groups is not None else 1
 
 
+def estimator_options(estimator):
+    """estimator= of Controller_batch, checked and with its defaults filled in (None stays None); unknown keys, of the dict and
+    of its kalman tuning, raise QrwError.  Touches no device: the constructors call it before they create a handle."""
+    if estimator is None:
+        return None
+    unknown = set(estimator) - {"h_init", "perfect", "kalman"}
+    if unknown:
+        raise qrw_hip.QrwError("estimator=: unknown keys %s (h_init, perfect, kalman)" % sorted(unknown))
+    kalman = estimator.get("kalman", False)
+    if kalman is False or kalman is None:
+        kalman = False
+    else:
+        qrw_hip.kalman_config(kalman)
+        kalman = True if kalman is True else dict(kalman)
+    return dict(h_init=float(estimator.get("h_init", 0.22294615)), perfect=bool(estimator.get("perfect", False)), kalman=kalman)
+
+
 class Controller_batch:
     def __new__(cls, batch, *args, groups=None, **kwargs):
         # more than one group: the fleet as independent stream groups, see Controller_groups
@@ -97,11 +114,14 @@ class Controller_batch:
         The masked streams are ordinary (blocking) HIP streams: they synchronise with the legacy default stream, so call
         compute() from a non-default stream (`with torch.cuda.stream(torch.cuda.Stream()): ...`) or the overlap is lost.
 
-        estimator=dict(h_init=..., perfect=False) (None = off, nothing changes): the state estimator on the device as well
-        (scripts/Estimator.py with the complementary filters, qrw_estimator_step), which enables compute_sensors(): IMU and
-        encoder readings in, Result out.  Its outputs live in the fleet-owned tensors q_filt / v_filt / rpy / v_secu."""
+        estimator=dict(h_init=..., perfect=False, kalman=False) (None = off, nothing changes): the state estimator on the device
+        as well (scripts/Estimator.py, qrw_estimator_step), which enables compute_sensors(): IMU and encoder readings in, Result
+        out.  kalman=False is the cascade of complementary filters (the reference's default), kalman=True its Kalman filter
+        (KFilterBis, kf_enabled=True) with the reference's tuning, a dict (sigma_kin, sigma_h, sigma_a, sigma_dp, gamma) the
+        same with other tuning.  The outputs live in the fleet-owned tensors q_filt / v_filt / rpy / v_secu."""
         import torch
 
+        estimator_options(estimator)  # (a bad option raises before a handle exists)
         self._torch = torch
         self.B = int(batch)
         self.dev = torch.device("cuda:%d" % device)
@@ -238,15 +258,13 @@ class Controller_batch:
 
     # ---- sensors in: the state estimator in front of the iteration (scripts/Controller.py:213)
     def _init_estimator(self, estimator, views=None):
-        """estimator: None (off) or dict(h_init=..., perfect=False).  views: a stream group's slices of the fleet's tensors."""
-        self.estimator = None if estimator is None else dict(h_init=float(estimator.get("h_init", 0.22294615)),
-                                                             perfect=bool(estimator.get("perfect", False)))
+        """estimator: None (off) or dict(h_init=..., perfect=False, kalman=False).  kalman: False (the complementary filters),
+        True (the Kalman filter with the reference's tuning) or a dict of qrw_hip.KALMAN_DEFAULTS values.  views: a stream
+        group's slices of the fleet's tensors."""
         self.q_filt = self.v_filt = self.rpy = self.v_secu = None
+        self.estimator = estimator_options(estimator)
         if self.estimator is None:
             return
-        unknown = set(estimator) - {"h_init", "perfect"}
-        if unknown:
-            raise qrw_hip.QrwError("estimator=: unknown keys %s (h_init, perfect)" % sorted(unknown))
         torch = self._torch
         if views is None:
             mk = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.dev)
@@ -488,6 +506,7 @@ class Controller_groups(Controller_batch):
                  stagger=None, deadline=None, estimator=None, _out_views=None):
         import torch
 
+        estimator_options(estimator)  # (a bad option raises before a handle exists)
         G = auto_groups(batch, groups, multiprocessing)
         stagger = bool(stagger)  # opt-in: it changes what the robots of the late groups do (see Controller_batch.__init__)
         if G < 2 or int(batch) % G:

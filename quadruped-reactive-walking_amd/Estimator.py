@@ -1,13 +1,17 @@
 """Drop-in for the reference's scripts/Estimator.py: `Estimator` with the complementary filters (kf_enabled=False, the
 reference's default, scripts/Controller.py:110-111) for ONE robot, on a batch-1 handle of libqrw_hip.so
-(qrw_estimator_step_host -> estimator_kernel.hip).  The fleet path is Controller_batch.compute_sensors.
+(qrw_estimator_step_host -> estimator_kernel.hip).  The fleet path is Controller_batch.compute_sensors, which has both of the
+reference's filters (estimator=dict(kalman=True) for KFilterBis).
 
 Provided: the constructor, run_filter(k, gait, device, goals), get_configurations(), EulerToQuaternion, quaternionToRPY, cross3
 and the attributes the reference's callers read (q_filt, v_filt, v_secu, RPY, alpha, FK_lin_vel, FK_xyz, xyz_mean_feet,
 filt_lin_vel, filt_lin_pos, close_from_contact, k_since_contact, feet_status, feet_goals, k_log, offset_yaw_IMU, the two
 filters' HP_x / LP_x / alpha, and the copies of the device's readings).
-Not provided: the Kalman variant (KFilter / KFilterBis; kf_enabled=True raises NotImplementedError), the log_* arrays and
-plot_graphs.  One departure: a gait whose rows all equal row 0 gives remaining_steps = N_gait where the reference raises
+Not provided HERE yet: the Kalman variant.  The library and the fleet path have it (qrw_estimator_init_kalman,
+qrw_hip.Batch.estimator_init(kalman=True)), but this single-robot drop-in still raises NotImplementedError for kf_enabled=True
+and has no `kf` / `Z` attributes: tests/test_estimator_cpu.py pins that refusal, and lifting it (a kalman=True on the batch-1
+handle, X / P / Z through estimator_kalman_get) belongs to a change that may touch that test.  Never provided: KFilter (which
+Estimator does not construct), the log_* arrays and plot_graphs.  One departure: a gait whose rows all equal row 0 gives remaining_steps = N_gait where the reference raises
 IndexError (scripts/Estimator.py:476-479)."""
 import numpy as np
 

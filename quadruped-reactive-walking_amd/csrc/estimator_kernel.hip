@@ -23,11 +23,20 @@
 // row 0; here the scan stops at N_gait.  Only an all-swing row 0 can do that (the unused rows of a gait matrix are zero rows),
 // which no gait of the planners produces.
 //
-// Out of scope: the Kalman variant (KFilter, KFilterBis, kf_enabled = True), the logging arrays and plot_graphs.
+// The Kalman variant (KFilterBis, kf_enabled = True, :88-181 and :555-580) is the second instantiation of the kernel: only the
+// block that replaces :519-553 differs.  Its arithmetic is kalman_filter.h (plain C++, also built for the host); here lanes 0, 1
+// and 2 of the quad each own one axis of the filter -- 6 states and a 6x6 block of P in registers, the three axes never couple --
+// and fetch their component of the four legs' measurement rows by quad permutes; lane 3 runs the z axis along with lane 2 and
+// stores nothing of it.  The z lanes take 8 scalar updates where x and y take 4: the kernel is launch-latency bound, it is not
+// balanced.  State of the filter: ks[item][B] (KalStateItem).  A robot whose readings are not finite keeps a non-finite filter
+// from then on, as in the reference; no permute leaves its quad.
+//
+// Out of scope: KFilter (the 6-state class nothing constructs), the logging arrays and plot_graphs.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "kalman_filter.h"
 #include "solo12_leg.h"
 #include "qrw_device.h"
 #include "qrw_kernels.h"
@@ -75,6 +84,9 @@ __device__ __forceinline__ M3 quat_to_rot(double x, double y, double z, double w
   return R;
 }
 
+static_assert(kKsP - kKsX == kf::kStates && kKsZ - kKsP == 3 * kf::kAxisStates * kf::kAxisStates && kKalStItems - kKsZ == kf::kMeas,
+              "KalStateItem is X, the three blocks of P, Z");
+
 struct ES {  // accessor of one instance's estimator state (item-major)
   double* base;
   size_t stride;  // = batch
@@ -91,9 +103,18 @@ __global__ __launch_bounds__(64) void estimator_init_kernel(EstimatorArgs a) {
   const ES s{a.es + b, (size_t)a.B};
   for (int i = 0; i < kEstStItems; i++) s(i) = 0.0;
   s(kEsFkXyz + 2) = a.h_init;
-  s(kEsLPp + 2) = a.h_init;
+  if (!a.kalman) {
+    s(kEsLPp + 2) = a.h_init;
+    return;
+  }
+  // kf_enabled (:284-285, :121): the height goes into X[2] instead, P = I; Z starts at zero (:301)
+  const ES k{a.ks + b, (size_t)a.B};
+  for (int i = 0; i < kKalStItems; i++) k(i) = 0.0;
+  k(kKsX + 2) = a.h_init;
+  for (int i = 0; i < 3 * 6; i++) k(kKsP + 36 * (i / 6) + 7 * (i % 6)) = 1.0;  // the diagonals of the three 6x6 blocks
 }
 
+template <bool KALMAN>
 __global__ __launch_bounds__(64) void estimator_kernel(EstimatorArgs a) {
   const int t = blockIdx.x * 64 + threadIdx.x;
   const int b = t >> 2, j = t & 3;
@@ -201,34 +222,8 @@ __global__ __launch_bounds__(64) void estimator_kernel(EstimatorArgs a) {
     close = 0.0;
   }
 
-  // ---- cascade of complementary filters (:521-553)
-  const V3 lever = mk(0.1163, 0.0, 0.02);  // _1Mi.translation (:323-324)
-  const V3 cross_product = cross(lever, gyro);
-  const V3 i_fk = fk_vel + cross_product;
-  const V3 oi_fk = mul(oRb, i_fk);
-  const V3 o_acc = mul(oRb, acc);
-  V3 hpv = s.v3(kEsHPv), lpv = s.v3(kEsLPv);
-  hpv = alpha * (hpv + a.dt * o_acc);             // ComplementaryFilter.compute (:223)
-  lpv = alpha * lpv + (1.0 - alpha) * oi_fk;      // (:226)
-  const V3 oi_filt = hpv + lpv;
-  const V3 i_filt = mulT(oRb, oi_filt);
-  const V3 b_filt = i_filt - cross_product;
-  const V3 ob_filt = mul(oRb, b_filt);
-  const V3 x_pos = fk_xyz + mean_feet;
-  V3 hpp = s.v3(kEsHPp), lpp = s.v3(kEsLPp);
-  const double axy = 0.995, az = 0.9;             // (:549-550)
-  hpp = mk(axy * (hpp.x + ob_filt.x * a.dt), axy * (hpp.y + ob_filt.y * a.dt), az * (hpp.z + ob_filt.z * a.dt));
-  lpp = mk(axy * lpp.x + (1.0 - axy) * x_pos.x, axy * lpp.y + (1.0 - axy) * x_pos.y, az * lpp.z + (1.0 - az) * x_pos.z);
-  V3 pos = hpp + lpp;
-
-  // ---- outputs (:594-624)
-  V3 v_new = b_filt;
-  if (a.perfect) {
-    pos.z = a.true_pos[(size_t)b * 3 + 2] - 0.0155;  // (:595-596)
-    v_new = mk(a.true_b_vel[(size_t)b * 3], a.true_b_vel[(size_t)b * 3 + 1], a.true_b_vel[(size_t)b * 3 + 2]);  // (:601-602)
-  }
-  const V3 v_old = s.v3(kEsVfilt);
-  const V3 v_lin = (1.0 - a.alpha_v) * v_old + a.alpha_v * v_new;
+  // ---- the outputs that do not wait for the filters (:597-598, :605-606, :624-627), stored first: the Kalman filter below
+  // needs the registers
   double* qf = a.q_filt + (size_t)b * 19;
   double* vf = a.v_filt + (size_t)b * 18;
   double* vs = a.v_secu + (size_t)b * 12;
@@ -243,19 +238,11 @@ __global__ __launch_bounds__(64) void estimator_kernel(EstimatorArgs a) {
   s(kEsKsc + j) = ksc;
   // the per-robot results: lanes 0..2 store component j of every 3-vector, lane 3 the scalars and the quaternion
   if (j < 3) {
-    qf[j] = pick(pos, j);
-    vf[j] = pick(v_lin, j);
     vf[3 + j] = pick(gyro, j);
     a.rpy[(size_t)b * 3 + j] = pick(rpy, j);
     s(kEsFkVel + j) = pick(fk_vel, j);
     s(kEsFkXyz + j) = pick(fk_xyz, j);
     s(kEsMeanFeet + j) = pick(mean_feet, j);
-    s(kEsHPv + j) = pick(hpv, j);
-    s(kEsLPv + j) = pick(lpv, j);
-    s(kEsHPp + j) = pick(hpp, j);
-    s(kEsLPp + j) = pick(lpp, j);
-    s(kEsFiltVel + j) = pick(b_filt, j);
-    s(kEsVfilt + j) = pick(v_lin, j);
   } else {
     qf[3] = qx; qf[4] = qy; qf[5] = qz; qf[6] = qw;
     s(kEsAlpha) = alpha;
@@ -263,11 +250,93 @@ __global__ __launch_bounds__(64) void estimator_kernel(EstimatorArgs a) {
     s(kEsYawOff) = yaw_off;
     s(kEsKlog) = k_log + 1.0;  // (:627)
   }
+
+  const V3 lever = mk(0.1163, 0.0, 0.02);  // _1Mi.translation (:323-324)
+  V3 pos, b_filt, hpv, lpv, hpp, lpp;
+  if constexpr (!KALMAN) {
+    // ---- cascade of complementary filters (:521-553)
+    const V3 cross_product = cross(lever, gyro);
+    const V3 i_fk = fk_vel + cross_product;
+    const V3 oi_fk = mul(oRb, i_fk);
+    const V3 o_acc = mul(oRb, acc);
+    hpv = s.v3(kEsHPv), lpv = s.v3(kEsLPv);
+    hpv = alpha * (hpv + a.dt * o_acc);             // ComplementaryFilter.compute (:223)
+    lpv = alpha * lpv + (1.0 - alpha) * oi_fk;      // (:226)
+    const V3 oi_filt = hpv + lpv;
+    const V3 i_filt = mulT(oRb, oi_filt);
+    b_filt = i_filt - cross_product;
+    const V3 ob_filt = mul(oRb, b_filt);
+    const V3 x_pos = fk_xyz + mean_feet;
+    hpp = s.v3(kEsHPp), lpp = s.v3(kEsLPp);
+    const double axy = 0.995, az = 0.9;             // (:549-550)
+    hpp = mk(axy * (hpp.x + ob_filt.x * a.dt), axy * (hpp.y + ob_filt.y * a.dt), az * (hpp.z + ob_filt.z * a.dt));
+    lpp = mk(axy * lpp.x + (1.0 - axy) * x_pos.x, axy * lpp.y + (1.0 - axy) * x_pos.y, az * lpp.z + (1.0 - az) * x_pos.z);
+    pos = hpp + lpp;
+  } else {
+    // ---- Kalman filter (:555-580): lane j < 3 owns axis j, lane 3 shadows lane 2
+    const int ax = j < 3 ? j : 2;
+    const ES ks{a.ks + b, B};
+    const V3 z = mul(oRb, lever - K.pf);  // this leg's rows 3j..3j+2 of Z (:569); its row 12+j is 0 (:570)
+    const V3 z0 = mk(quad_bcast<0>(z.x), quad_bcast<0>(z.y), quad_bcast<0>(z.z));
+    const V3 z1 = mk(quad_bcast<1>(z.x), quad_bcast<1>(z.y), quad_bcast<1>(z.z));
+    const V3 z2 = mk(quad_bcast<2>(z.x), quad_bcast<2>(z.y), quad_bcast<2>(z.z));
+    const V3 z3 = mk(quad_bcast<3>(z.x), quad_bcast<3>(z.y), quad_bcast<3>(z.z));
+    const double z_kin[4] = {pick(z0, ax), pick(z1, ax), pick(z2, ax), pick(z3, ax)};
+    const double st4[4] = {quad_bcast<0>(status), quad_bcast<1>(status), quad_bcast<2>(status), quad_bcast<3>(status)};
+    const kf::Tuning tune{a.kf_sigma_kin, a.kf_sigma_h, a.kf_sigma_a, a.kf_sigma_dp, a.kf_gamma};
+    const kf::Coeffs co = kf::update_coeffs(tune, a.dt, st4);  // updateCoeffs (:167-181)
+    const V3 o_acc = mul(oRb, acc);
+    kf::Axis A;
+#pragma unroll
+    for (int k = 0; k < 6; k++) A.x[k] = ks(kKsX + kf::state_index(ax, k));
+#pragma unroll
+    for (int k = 0; k < 36; k++) A.p[k] = ks(kKsP + 36 * ax + k);
+    kf::axis_step(A, ax == 2, a.dt, pick(o_acc, ax), z_kin, co);  // predict (:152-157), correct (:159-165)
+    if (j < 3) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) ks(kKsX + kf::state_index(ax, k)) = A.x[k];
+#pragma unroll
+      for (int k = 0; k < 36; k++) ks(kKsP + 36 * ax + k) = A.p[k];
+    }
+    ks(kKsZ + 3 * j) = z.x; ks(kKsZ + 3 * j + 1) = z.y; ks(kKsZ + 3 * j + 2) = z.z;
+    ks(kKsZ + 12 + j) = 0.0;
+    // results (:578-580)
+    const double xp[3] = {quad_bcast<0>(A.x[0]), quad_bcast<1>(A.x[0]), quad_bcast<2>(A.x[0])};
+    const double xv[3] = {quad_bcast<0>(A.x[1]), quad_bcast<1>(A.x[1]), quad_bcast<2>(A.x[1])};
+    pos = mk(kf::base_position(0, xp[0]), kf::base_position(1, xp[1]), kf::base_position(2, xp[2]));
+    const double R9[9] = {oRb.r0.x, oRb.r0.y, oRb.r0.z, oRb.r1.x, oRb.r1.y, oRb.r1.z, oRb.r2.x, oRb.r2.y, oRb.r2.z};
+    const double g3[3] = {gyro.x, gyro.y, gyro.z};
+    double bv[3];
+    kf::base_velocity(R9, xv, g3, bv);
+    b_filt = mk(bv[0], bv[1], bv[2]);
+  }
+
+  // ---- the filtered position and velocity (:594-604)
+  V3 v_new = b_filt;
+  if (a.perfect) {
+    pos.z = a.true_pos[(size_t)b * 3 + 2] - 0.0155;  // (:595-596)
+    v_new = mk(a.true_b_vel[(size_t)b * 3], a.true_b_vel[(size_t)b * 3 + 1], a.true_b_vel[(size_t)b * 3 + 2]);  // (:601-602)
+  }
+  const V3 v_old = s.v3(kEsVfilt);
+  const V3 v_lin = (1.0 - a.alpha_v) * v_old + a.alpha_v * v_new;
+  if (j < 3) {
+    qf[j] = pick(pos, j);
+    vf[j] = pick(v_lin, j);
+    if constexpr (!KALMAN) {  // (the reference leaves the complementary filters alone in Kalman mode)
+      s(kEsHPv + j) = pick(hpv, j);
+      s(kEsLPv + j) = pick(lpv, j);
+      s(kEsHPp + j) = pick(hpp, j);
+      s(kEsLPp + j) = pick(lpp, j);
+    }
+    s(kEsFiltVel + j) = pick(b_filt, j);
+    s(kEsVfilt + j) = pick(v_lin, j);
+  }
 }
 
 int estimator_launch(const EstimatorArgs& a, hipStream_t stream) {
   if (a.init) hipLaunchKernelGGL(estimator_init_kernel, dim3((a.B + 63) / 64), dim3(64), 0, stream, a);
-  else hipLaunchKernelGGL(estimator_kernel, dim3((a.B + 15) / 16), dim3(64), 0, stream, a);
+  else if (a.kalman) hipLaunchKernelGGL(estimator_kernel<true>, dim3((a.B + 15) / 16), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(estimator_kernel<false>, dim3((a.B + 15) / 16), dim3(64), 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

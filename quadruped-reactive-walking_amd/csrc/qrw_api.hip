@@ -1,10 +1,12 @@
 // Host side of libqrw_hip.so: the C ABI declared in include/qrw_hip.h (all of it but qrw_selftest_sweeps: qrw_selftest.hip).
 // Owns the per-instance persistent solver state in HBM and launches the gfx950 kernels.
 // There is NO CPU fallback: every entry point needs a HIP device and fails loudly otherwise.
+#include <cmath>
 #include <mutex>
 #include <string>
 
 #include "../../include/qrw_solo12_model.h"
+#include "kalman_filter.h"
 #include "qrw_host.h"
 
 using namespace qrw::host;
@@ -171,13 +173,13 @@ extern "C" int qrw_destroy(qrw_handle h) {
   return 0;
 }
 
-// (the persistent solver state of the MPC and the WBC and the estimator's filters: not the diagnostics, planner, controller,
-// staging or queue buffers)
+// (the persistent solver state of the MPC and the WBC and the estimator's filters -- the Kalman filter's once a handle has
+// allocated it: not the diagnostics, planner, controller, staging or queue buffers)
 extern "C" int64_t qrw_state_bytes(qrw_handle h) {
   if (!h) return 0;
   return (int64_t)(h->mpc_st.bytes + h->mpc_gait.bytes + h->mpc_flags.bytes + h->mpc_iters.bytes + h->mpc_status.bytes +
                    h->mpc_rho_updates.bytes + h->mpc_order.bytes + h->mpc_ema.bytes + h->mpc_rho.bytes + h->mpc_pri.bytes +
-                   h->mpc_dua.bytes + h->wbc_st.bytes + h->wbc_iters.bytes + h->wbc_status.bytes + h->est_st.bytes + h->sim_st.bytes);
+                   h->mpc_dua.bytes + h->wbc_st.bytes + h->wbc_iters.bytes + h->wbc_status.bytes + h->est_st.bytes + h->kal_st.bytes + h->sim_st.bytes);
 }
 
 // what every MPC launch of a handle is told about its persistent state; xref / fsteps / out as the caller lays them out
@@ -813,20 +815,45 @@ static qrw::EstimatorArgs estimator_common(qrw_handle h) {
   a.B = h->cfg.batch; a.N_gait = h->cfg.N_gait; a.perfect = h->ecfg.perfect ? 1 : 0;
   a.dt = h->cfg.dt_wbc; a.h_init = h->ecfg.h_init; a.alpha_v = h->est_alpha_v; a.alpha_secu = h->est_alpha_secu;
   a.es = h->est_st;
+  a.kalman = h->est_kalman ? 1 : 0;
+  if (h->est_kalman) {
+    a.ks = h->kal_st;
+    a.kf_sigma_kin = h->kcfg.sigma_kin; a.kf_sigma_h = h->kcfg.sigma_h; a.kf_sigma_a = h->kcfg.sigma_a;
+    a.kf_sigma_dp = h->kcfg.sigma_dp; a.kf_gamma = h->kcfg.gamma;
+  }
   return a;
 }
-
-extern "C" int qrw_estimator_init(qrw_handle h, const qrw_estimator_config* cfg, void* stream) {
-  QRW_ENTER(h, !cfg, "qrw_estimator_init: null argument");
+// Estimator.__init__ for the filter `kalman` chooses: the handle's mode, its filter coefficients, the init launch
+static int estimator_reset(qrw_handle h, const qrw_estimator_config* cfg, bool kalman, void* stream, const char* failed) {
   h->ecfg = *cfg;
+  h->est_kalman = kalman;
   h->est_alpha_v = filter_alpha(50.0, h->cfg.dt_wbc);
   h->est_alpha_secu = filter_alpha(6.0, h->cfg.dt_wbc);
   qrw::EstimatorArgs a = estimator_common(h);
   a.init = 1;
-  if (qrw::estimator_launch(a, (hipStream_t)stream) != 0) return fail(-11, "qrw_estimator_init: launch failed", hipGetLastError());
+  if (qrw::estimator_launch(a, (hipStream_t)stream) != 0) return fail(-11, failed, hipGetLastError());
   note_launch(h, kFamEst, (hipStream_t)stream);
   h->est_ready = true;
   return 0;
+}
+
+extern "C" int qrw_estimator_init(qrw_handle h, const qrw_estimator_config* cfg, void* stream) {
+  QRW_ENTER(h, !cfg, "qrw_estimator_init: null argument");
+  return estimator_reset(h, cfg, false, stream, "qrw_estimator_init: launch failed");
+}
+
+extern "C" int qrw_estimator_init_kalman(qrw_handle h, const qrw_estimator_config* cfg, const qrw_kalman_config* kcfg, void* stream) {
+  QRW_ENTER(h, !cfg, "qrw_estimator_init_kalman: null argument");
+  const qrw_kalman_config k = kcfg ? *kcfg : qrw_kalman_config{0.1, 1.0, 0.1, 0.1, 30.0};  // (scripts/Estimator.py:133-137)
+  for (const double sigma : {k.sigma_kin, k.sigma_h, k.sigma_a, k.sigma_dp})
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(-1, "qrw_estimator_init_kalman: the sigmas must be > 0 and finite");
+  if (!std::isfinite(k.gamma)) return fail(-1, "qrw_estimator_init_kalman: gamma must be finite");
+  if (!h->kal_st) {  // (the init kernel writes every item: no fill)
+    const hipError_t e = h->kal_st.alloc((size_t)h->cfg.batch * qrw::kKalStItems);
+    if (e != hipSuccess) return fail(-10, "qrw_estimator_init_kalman: hipMalloc kal_st", e);
+  }
+  h->kcfg = k;
+  return estimator_reset(h, cfg, true, stream, "qrw_estimator_init_kalman: launch failed");
 }
 
 extern "C" int qrw_estimator_step(qrw_handle h, const double* d_lin_acc, const double* d_ang_vel, const double* d_quat,
@@ -890,6 +917,29 @@ extern "C" int qrw_estimator_get_host(qrw_handle h, int32_t which, int32_t b, in
   HIP_OK(hipMemcpy2DAsync(h_out, sizeof(double), h->est_st + (size_t)kOff[which] * B + b, B * sizeof(double), sizeof(double), count,
                           hipMemcpyDeviceToHost, h->host_stream), "qrw_estimator_get_host: D2H estimator state");
   HIP_OK(host_done(h), "qrw_estimator_get_host: D2H estimator state");
+  return 0;
+}
+
+extern "C" int qrw_estimator_kalman_get_host(qrw_handle h, int32_t which, int32_t b, int32_t count, double* h_out) {
+  QRW_ENTER_HOST(h, !h_out || b < 0 || b >= h->cfg.batch || count < 1, "qrw_estimator_kalman_get_host: bad argument");
+  if (!h->est_ready || !h->est_kalman) return fail(-1, "qrw_estimator_kalman_get_host: not in Kalman mode");
+  static const int kLen[3] = {qrw::kf::kStates, qrw::kf::kStates * qrw::kf::kStates, qrw::kf::kMeas};
+  if (which < 0 || which >= 3 || count > kLen[which]) return fail(-1, "qrw_estimator_kalman_get_host: bad item");
+  const size_t B = h->cfg.batch;
+  HIP_OK(wait_family(h, kFamEst), "qrw_estimator_kalman_get_host: earlier estimator step of this handle");
+  double blocks[3 * 36];
+  const int off = which == 0 ? qrw::kKsX : which == 1 ? qrw::kKsP : qrw::kKsZ;
+  const int items = which == 1 ? 3 * 36 : count;
+  HIP_OK(hipMemcpy2DAsync(which == 1 ? blocks : h_out, sizeof(double), h->kal_st + (size_t)off * B + b, B * sizeof(double),
+                          sizeof(double), items, hipMemcpyDeviceToHost, h->host_stream), "qrw_estimator_kalman_get_host: D2H filter state");
+  HIP_OK(host_done(h), "qrw_estimator_kalman_get_host: D2H filter state");
+  if (which == 1) {  // the dense P from the per-axis blocks: exact zeros between the axes
+    double P[qrw::kf::kStates * qrw::kf::kStates];
+    qrw::kf::Filter f;
+    for (int j = 0; j < 3; j++) memcpy(f.axis[j].p, blocks + 36 * j, sizeof(f.axis[j].p));
+    qrw::kf::filter_covariance(f, P);
+    memcpy(h_out, P, (size_t)count * sizeof(double));
+  }
   return 0;
 }
 

@@ -116,6 +116,9 @@ struct qrw_handle_s {
   qrw_estimator_config ecfg;
   double est_alpha_v = 0.0, est_alpha_secu = 0.0;
   bool est_ready = false;
+  DevBuf<double> kal_st;     // the Kalman variant's state, allocated by the first qrw_estimator_init_kalman
+  qrw_kalman_config kcfg;
+  bool est_kalman = false;   // which filter the last initialisation chose
   // rigid-body simulator: its state, its parameters, and the measurement buffers of the host-buffer entry points (allocated by
   // qrw_sim_init_host: a frozen robot's rows keep their last finite values there, as in a caller's device buffers)
   DevBuf<double> sim_st, sim_out;

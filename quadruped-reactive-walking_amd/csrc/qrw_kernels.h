@@ -197,8 +197,18 @@ enum EstStateItem {
   kEsVsecu = 35,     // v_secu of the previous call (12)
   kEstStItems = 47
 };
+// the Kalman variant's state: ks[item][B], allocated at the handle's first qrw_estimator_init_kalman
+enum KalStateItem {
+  kKsX = 0,    // X (18): base position, base velocity, the four foot positions
+  kKsP = 18,   // the three per-axis 6x6 blocks of P, full, row-major (3 x 36): block j couples the states kf::state_index(j, .)
+  kKsZ = 126,  // the last measurement Z (16)
+  kKalStItems = 142
+};
 struct EstimatorArgs {
   int B, N_gait, init, perfect;
+  int kalman;                                              // 0 complementary filters, 1 Kalman filter (ks and kf_* below)
+  double kf_sigma_kin, kf_sigma_h, kf_sigma_a, kf_sigma_dp, kf_gamma;
+  double* ks;                                              // [kKalStItems][B]
   double dt, h_init, alpha_v, alpha_secu;
   const double *lin_acc, *ang_vel, *quat, *q_mes, *v_mes;  // [B][3], [B][3], [B][4] xyzw, [B][12], [B][12]
   const double *gait, *goals;                              // [B][N_gait][4], [B][3][4]; null = the planner state below

@@ -36,6 +36,23 @@ class _EstimatorConfig(C.Structure):
 ESTIMATOR_ITEMS = {"k_since_contact": (0, 4), "FK_lin_vel": (1, 3), "FK_xyz": (2, 3), "xyz_mean_feet": (3, 3),
                    "HP_lin_vel": (4, 3), "LP_lin_vel": (5, 3), "HP_lin_pos": (6, 3), "LP_lin_pos": (7, 3), "alpha": (8, 1),
                    "close_from_contact": (9, 1), "offset_yaw_IMU": (10, 1), "k_log": (11, 1), "filt_lin_vel": (12, 3)}
+# qrw_kalman_config, field for field, with the reference's values (scripts/Estimator.py:133-137)
+KALMAN_DEFAULTS = dict(sigma_kin=0.1, sigma_h=1.0, sigma_a=0.1, sigma_dp=0.1, gamma=30.0)
+# qrw_estimator_kalman_get_host: item -> (which, shape)
+KALMAN_ITEMS = {"X": (0, (18,)), "P": (1, (18, 18)), "Z": (2, (16,))}
+
+
+class _KalmanConfig(C.Structure):
+    _fields_ = [(n, C.c_double) for n in KALMAN_DEFAULTS]
+
+
+def kalman_config(kalman):
+    """kalman=True (the reference's tuning) or a dict of some of KALMAN_DEFAULTS -> _KalmanConfig."""
+    values = {} if kalman is True else dict(kalman)
+    unknown = set(values) - set(KALMAN_DEFAULTS)
+    if unknown:
+        raise QrwError("kalman=: unknown keys %s (%s)" % (sorted(unknown), ", ".join(KALMAN_DEFAULTS)))
+    return _KalmanConfig(*[float(dict(KALMAN_DEFAULTS, **values)[n]) for n in KALMAN_DEFAULTS])
 
 
 class _SimParams(C.Structure):
@@ -123,6 +140,8 @@ SIGNATURES = {
     "qrw_iteration_bind": (C.c_int, [_vp, C.POINTER(_IterationBuffers)]),
     "qrw_iteration_step": (C.c_int, [_vp, C.c_int32, _vp, _vp]),
     "qrw_estimator_init": (C.c_int, [_vp, _vp, _vp]),
+    "qrw_estimator_init_kalman": (C.c_int, [_vp, _vp, C.POINTER(_KalmanConfig), _vp]),
+    "qrw_estimator_kalman_get_host": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "qrw_estimator_step": (C.c_int, [_vp] + [_vp] * 13 + [_vp]),
     "qrw_estimator_step_host": (C.c_int, [_vp] + [_dp] * 13),
     "qrw_estimator_get_host": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _dp]),
@@ -656,12 +675,20 @@ class Batch:
 
         return step
 
-    # ------------------------------------------------ state estimator (scripts/Estimator.py, complementary filters)
-    def estimator_init(self, h_init=0.22294615, perfect=False):
-        """Estimator.__init__ (scripts/Estimator.py:245-342) for every instance; again = re-initialise."""
+    # ------------------------------------------------ state estimator (scripts/Estimator.py, either of its two filters)
+    def estimator_init(self, h_init=0.22294615, perfect=False, kalman=False):
+        """Estimator.__init__ (scripts/Estimator.py:245-342) for every instance; again = re-initialise.  kalman: False = the
+        complementary filters (kf_enabled=False), True = the Kalman filter (KFilterBis) with the reference's tuning, or a dict
+        of some of KALMAN_DEFAULTS (sigma_kin, sigma_h, sigma_a, sigma_dp, gamma); unknown keys raise QrwError."""
         ec = _EstimatorConfig(float(h_init), int(bool(perfect)))
-        _check(self._lib.qrw_estimator_init(self._handle, C.cast(C.byref(ec), _vp), self._stream()), "qrw_estimator_init")
+        if kalman is False or kalman is None:
+            _check(self._lib.qrw_estimator_init(self._handle, C.cast(C.byref(ec), _vp), self._stream()), "qrw_estimator_init")
+        else:
+            kc = kalman_config(kalman)
+            _check(self._lib.qrw_estimator_init_kalman(self._handle, C.cast(C.byref(ec), _vp), C.byref(kc), self._stream()),
+                   "qrw_estimator_init_kalman")
         self.estimator_perfect = bool(perfect)
+        self.estimator_kalman = not (kalman is False or kalman is None)
 
     def estimator_step(self, lin_acc, ang_vel, quat, q_mes, v_mes, gait=None, goals=None, true_pos=None, true_b_vel=None,
                        out=None):
@@ -700,6 +727,15 @@ class Batch:
         which, count = ESTIMATOR_ITEMS[item]
         out = np.empty(count)
         _check(self._lib.qrw_estimator_get_host(self._handle, which, int(b), count, _p(out)), "qrw_estimator_get_host")
+        return out
+
+    def estimator_kalman_get(self, item, b=0):
+        """The Kalman filter's state of instance b (KALMAN_ITEMS): "X" (18), "P" (18, 18) or "Z" (16, the last measurement) as a
+        numpy array; QrwError unless the estimator was initialised with kalman=..."""
+        which, shape = KALMAN_ITEMS[item]
+        out = np.empty(shape)
+        _check(self._lib.qrw_estimator_kalman_get_host(self._handle, which, int(b), out.size, _p(out)),
+               "qrw_estimator_kalman_get_host")
         return out
 
     # ------------------------------------------------ rigid-body simulator (csrc/sim_kernel.hip)

@@ -2,6 +2,7 @@
 qrw_control_pre launch of the same run (the yardstick):
 
     python scripts/gpu_estimator_timing.py [rounds=10] [calls per round and leg=200]   ->  profiles/estimator_timing.json
+    python scripts/gpu_estimator_timing.py --kalman [rounds] [calls]                   ->  profiles/estimator_kalman_timing.json
 
 Batch 4096 and 256, one process, the four legs alternating round by round (>= 2000 calls per leg in all):
   (a) iteration        the state-in non-solving iteration, qrw_iteration_step (control_pre + wbc_compute_result)
@@ -10,7 +11,11 @@ Batch 4096 and 256, one process, the four legs alternating round by round (>= 20
   (d) control_pre      qrw_control_pre alone (non-solving form)
 Two figures per leg, microseconds per call: `device` = the calls queued behind a blocker kernel and timed by two events once it
 ends (back-to-back on the device, no host in the window); `issued` = the same calls timed while the host issues them (what a
-free-running loop sees: the larger of host issue time and device time).  (b) - (a) is the cost of the extra launch."""
+free-running loop sees: the larger of host issue time and device time).  (b) - (a) is the cost of the extra launch.
+
+--kalman: the Kalman variant of the estimator (qrw_estimator_init_kalman) against the complementary one at the same commit, the
+yardstick: two handles of the same batch in one process, the legs `estimator` (complementary) and `kalman_estimator` and the two
+`est+iteration` legs alternating round by round, same method."""
 import json
 import os
 import sys
@@ -23,15 +28,17 @@ import torch  # noqa: E402
 import synth  # noqa: E402
 from Controller import Controller_batch  # noqa: E402
 
-ROUNDS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-CALLS = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+KALMAN = "--kalman" in sys.argv
+ARGS = [a for a in sys.argv[1:] if a != "--kalman"]
+ROUNDS = int(ARGS[0]) if len(ARGS) > 0 else 10
+CALLS = int(ARGS[1]) if len(ARGS) > 1 else 200
 Q_INIT = np.array([0.0, 0.7, -1.4, -0.0, 0.7, -1.4, 0.0, -0.7, +1.4, -0.0, -0.7, +1.4])
 LEGS = ("iteration", "est+iteration", "estimator", "control_pre")
 
 
-def legs_of(B, dev):
+def legs_of(B, dev, kalman=False):
     """The four legs as argument-free callables on warmed, bound buffers (every call is one or two foreign calls)."""
-    ctl = Controller_batch(B, Q_INIT, estimator=dict(h_init=0.22294615))
+    ctl = Controller_batch(B, Q_INIT, estimator=dict(h_init=0.22294615, kalman=kalman))
     sen = synth.SyntheticSensors(B, 1)
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     vref = t(np.tile(np.array([0.3, 0.0, 0, 0, 0, 0.1]), (B, 1)))
@@ -84,9 +91,39 @@ def timed(fn, calls, blocked):
     return 1e3 * a.elapsed_time(b) / calls
 
 
+def main_kalman(dev):
+    """The Kalman estimator step against the complementary one: alone and in front of the iteration."""
+    names = ("estimator", "kalman_estimator", "est+iteration", "kalman_est+iteration")
+    out = {"rounds": ROUNDS, "calls_per_round": CALLS, "unit": "us per call", "batches": {}}
+    with torch.cuda.stream(torch.cuda.Stream(dev)):
+        for B in (4096, 256):
+            (ctl_c, legs_c), (ctl_k, legs_k) = legs_of(B, dev), legs_of(B, dev, kalman=True)
+            legs = dict(zip(names, (legs_c["estimator"], legs_k["estimator"], legs_c["est+iteration"], legs_k["est+iteration"])))
+            for fn in legs.values():
+                timed(fn, CALLS, False)
+            rec = {name: {"device": [], "issued": []} for name in names}
+            for _ in range(ROUNDS):
+                for name in names:
+                    rec[name]["device"].append(timed(legs[name], CALLS, True))
+                for name in names:
+                    rec[name]["issued"].append(timed(legs[name], CALLS, False))
+            res = {name: {kind: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+                          for kind, v in kinds.items()} for name, kinds in rec.items()}
+            res["kalman_over_complementary_device"] = res["kalman_estimator"]["device"]["median"] / res["estimator"]["device"]["median"]
+            res["kalman_extra_per_iteration_device"] = (res["kalman_est+iteration"]["device"]["median"]
+                                                        - res["est+iteration"]["device"]["median"])
+            res["error_flags_set"] = int((ctl_c.error_flag != 0).sum().item()) + int((ctl_k.error_flag != 0).sum().item())
+            out["batches"][str(B)] = res
+            print(B, json.dumps(res))
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    json.dump(out, open(os.path.join(ROOT, "profiles", "estimator_kalman_timing.json"), "w"), indent=1, sort_keys=True)
+
+
 def main():
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda", 0)
+    if KALMAN:
+        return main_kalman(dev)
     out = {"rounds": ROUNDS, "calls_per_round": CALLS, "unit": "us per call", "batches": {}}
     with torch.cuda.stream(torch.cuda.Stream(dev)):
         for B in (4096, 256):
