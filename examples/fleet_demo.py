@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A fleet of Solo12 robots stepped by the device-resident control loop, paced at the reference's 2 ms (src/config_solo12.yaml:6).
 
-    python examples/fleet_demo.py [robots] [seconds] [sync|async|auto] [--sensors | --sim] [--kalman] [--vx=V]
+    python examples/fleet_demo.py [robots] [seconds] [sync|async|auto] [--sensors | --sim [--rough [--spread]]] [--kalman] [--vx=V]
 
 `Controller_batch` mirrors `Controller.compute` of the reference (scripts/Controller.py:200-326) for B robots: the estimator's
 outputs go in (reference velocity, filtered q / v, roll-pitch, joint velocities), the PD targets and feed-forward torques come out;
@@ -14,7 +14,11 @@ a flat plane, one more kernel per tick) takes the PD targets and torques and del
 without an error flag and without a simulator status are counted and the distance they covered is printed, next to the distance
 the estimator reads.  --kalman (implies --sensors unless --sim is given) runs the estimator with the reference's Kalman filter
 (KFilterBis, kf_enabled=True) instead of its complementary filters.  --vx=V gives every robot the forward reference speed V and
-no yaw rate (default: 0 to 0.4 m/s and -0.3 to 0.3 rad/s, drawn per robot)."""
+no yaw rate (default: 0 to 0.4 m/s and -0.3 to 0.3 rad/s, drawn per robot).
+--rough (with --sim) puts the fleet on the heightfield the reference builds for use_flat_plane=False
+(Simulator.reference_rough_ground: 512 x 512 samples, 5 cm cells, bumps to 5 cm); all robots then start on the same patch, at the
+field's centre, unless --spread gives each an origin of its own on a square grid inside the field.  The controller and the
+estimator assume flat ground: how many robots keep their feet is what this prints, not something it expects."""
 import os
 import sys
 import time
@@ -26,13 +30,16 @@ import torch  # noqa: E402
 
 import synth  # noqa: E402
 from Controller import Controller_batch  # noqa: E402
-from Simulator import Simulator_batch  # noqa: E402
+from Simulator import Simulator_batch, reference_rough_ground  # noqa: E402
 
 sim_on = "--sim" in sys.argv
 kalman = "--kalman" in sys.argv
+rough, spread = "--rough" in sys.argv, "--spread" in sys.argv
+if (rough and not sim_on) or (spread and not rough):
+    sys.exit("--rough needs --sim, --spread needs --rough")
 sensors = ("--sensors" in sys.argv or kalman) and not sim_on
 vx = [float(a[5:]) for a in sys.argv if a.startswith("--vx=")]
-argv = [a for a in sys.argv if a not in ("--sensors", "--sim", "--kalman") and not a.startswith("--vx=")]
+argv = [a for a in sys.argv if a not in ("--sensors", "--sim", "--kalman", "--rough", "--spread") and not a.startswith("--vx=")]
 B = int(argv[1]) if len(argv) > 1 else 1024
 seconds = float(argv[2]) if len(argv) > 2 else 1.0
 mode = argv[3] if len(argv) > 3 else "sync"
@@ -65,7 +72,14 @@ with torch.cuda.stream(torch.cuda.Stream(dev)):  # (keep the caller's work off t
         sen = synth.SyntheticSensors(B, 0) if sensors else None
         names = ("lin_acc", "ang_vel", "quat", "q_mes", "v_mes")
         s_dev = {n: torch.empty(v.shape, dtype=torch.float64, device=dev) for n, v in sen.step(0).items()} if sensors else None
-        sim = Simulator_batch(B, q_init, controller=ctl) if sim_on else None
+        ground = reference_rough_ground() if rough else None
+        origin = None
+        if spread:  # a square grid of patches, 2 m clear of the field's edge (a robot covers a metre or so in a run)
+            side = int(np.ceil(np.sqrt(B)))
+            reach = -ground["x0"] - 2.0
+            at = np.linspace(-reach, reach, side) if side > 1 else np.zeros(1)
+            origin = np.stack(np.meshgrid(at, at), axis=-1).reshape(-1, 2)[:B].copy()
+        sim = Simulator_batch(B, q_init, controller=ctl, terrain=ground, terrain_origin=origin) if sim_on else None
         lat, nxt = [], time.perf_counter()
         for k in range(int(seconds / 0.002)):
             while time.perf_counter() < nxt:
@@ -107,5 +121,5 @@ lat = np.array(lat)
 warm = lat[20:]  # the first two MPC solves start cold (QP set-up, ~1 000 ADMM iterations): like the reference's first iterations
 print("%d robots, %s mode%s, %d ticks paced at 2 ms: tick latency median %.3f ms, worst %.3f ms after the first 20 ticks (%d ticks over the slot; "
       "cold start: %.3f ms); largest |tau_ff| %.2f N m; robots in security stop %d%s"
-      % (B, mode, (", simulator in the loop" if sim_on else ", sensors in" if sensors else "") + (", Kalman estimator" if kalman else ""), len(lat), np.median(lat), warm.max(),
+      % (B, mode, (", simulator in the loop" + (" on the reference's rough ground" + (", one patch per robot" if spread else ", one patch for all") if rough else "") if sim_on else ", sensors in" if sensors else "") + (", Kalman estimator" if kalman else ""), len(lat), np.median(lat), warm.max(),
          int((warm > 2.0).sum()), lat[:20].max(), tau, stopped, sim_line if sim_on else ""))

@@ -386,7 +386,8 @@ int qrw_estimator_kalman_get_host(qrw_handle h, int32_t which, int32_t b, int32_
  * tau = tau_ff + P (q_des - q) + D (v_des - dq) from the joint state at the start of the tick, held over `substeps` semi-implicit
  * Euler steps of the forward dynamics, then the readings qrw_estimator_step takes, in its layouts.  The physics is NOT
  * PyBullet's: penalty contact (fn = max(0, kn d - dn vz) while the penetration d = foot_radius - z_foot > 0, friction
- * -mu fn v_t / sqrt(|v_t|^2 + vs^2)) on the plane z = 0 only; no joint limits, no joint friction, no motor model.
+ * -mu fn v_t / sqrt(|v_t|^2 + vs^2)) on the plane z = 0, or on a heightfield (qrw_sim_set_terrain below); no joint limits, no
+ * joint friction, no motor model.
  * State per instance, QRW_SIM_STATE_ITEMS doubles: q19 (position, quaternion xyzw, joints FL FR HL HR), v18 (base linear and
  * angular velocity in the base frame, joint velocities), prev_o_imuVel (3), tick counter, status.  A robot whose new state is not
  * finite gets status 1 and is frozen: nothing of that tick or a later one is stored for it (its rows of the output buffers keep
@@ -412,7 +413,8 @@ typedef struct {
   double *d_joint_torques;        /* [B][12] */
 } qrw_sim_buffers;
 
-/* Sets the state (d_q_init [B][q_ld]: q_ld = 19 the whole q19, q_ld = 12 the joints with the base level at params->base_height;
+/* Sets the state (d_q_init [B][q_ld]: q_ld = 19 the whole q19, q_ld = 12 the joints with the base level at params->base_height
+ * (above the highest ground under its feet when a terrain is set);
  * velocities, prev_o_imuVel, tick and status zero) and writes the first measurement, as the reference's first UpdateMeasurment.
  * Again = re-initialise. */
 int qrw_sim_init(qrw_handle h, const double *d_q_init, int32_t q_ld, const qrw_sim_params *params, const qrw_sim_buffers *out,
@@ -432,6 +434,23 @@ int qrw_sim_step_host(qrw_handle h, const double *h_P, const double *h_D, const 
  * not rewrite the measurement buffers. */
 int qrw_sim_get_host(qrw_handle h, double *h_state);
 int qrw_sim_set_host(qrw_handle h, const double *h_state);
+
+/* Heightfield terrain instead of the plane z = 0: ONE field per handle, shared by all its robots.  Heights [rows][cols] in C
+ * order, rows, cols >= 2; vertex (r, c) lies at world x = x0 + c dx, y = y0 + r dy (dx, dy > 0).  Every cell is cut by the diagonal
+ * from (r, c) to (r+1, c+1) and a foot is in contact with the plane of the triangle under it: with its unit normal n,
+ * d = foot_radius - n_z (z_foot - h), normal force kn d - dn (n.v) clipped at 0 while d > 0, friction against the tangential
+ * velocity as on the plane (a field of zeros IS the plane's formula).  d_origin_xy [B][2], or NULL: robot b's feet at world
+ * (x, y) are looked up at (x + ox[b], y + oy[b]), so that every robot can walk a patch of its own.  Outside the field the
+ * surface continues as the clamped point of the edge cell (unphysical; never a fault, whatever the coordinate).
+ * The handle keeps a copy of its own (device-to-device on `stream`, ordered like a tick; reallocated only when the size
+ * changes).  The setting survives qrw_sim_init; qrw_sim_init with q_ld = 12 then puts the level base at (0, 0) base_height above
+ * the highest ground under its four feet.  Refused (-1): rows or cols < 2, a spacing that is not positive and finite, NULL
+ * heights.  _host: the same from host pointers, synchronised per handle.  qrw_sim_clear_terrain: back to the plane. */
+int qrw_sim_set_terrain(qrw_handle h, const double *d_heights, int32_t rows, int32_t cols, double x0, double y0, double dx,
+                        double dy, const double *d_origin_xy, void *stream);
+int qrw_sim_set_terrain_host(qrw_handle h, const double *h_heights, int32_t rows, int32_t cols, double x0, double y0, double dx,
+                             double dy, const double *h_origin_xy);
+int qrw_sim_clear_terrain(qrw_handle h);
 
 /* ---------------- asynchronous MPC ----------------
  * The reference runs the MPC in a child process on its own CPU core and polls a shared flag

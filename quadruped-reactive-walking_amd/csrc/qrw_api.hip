@@ -963,6 +963,7 @@ static qrw::SimArgs sim_common(qrw_handle h, int mode, const qrw_sim_buffers* o)
   a.q_mes = o->d_q_mes; a.v_mes = o->d_v_mes; a.quat = o->d_quat; a.ang_vel = o->d_ang_vel; a.lin_acc = o->d_lin_acc;
   a.o_imu_vel = o->d_o_imu_vel; a.true_pos = o->d_true_pos; a.true_b_vel = o->d_true_b_vel;
   a.contact_forces = o->d_contact_forces; a.joint_torques = o->d_joint_torques;
+  sim_terrain_args(h, a);
   return a;
 }
 // the handle's own measurement buffers (host-buffer entry points), carved out of sim_out
@@ -1074,6 +1075,66 @@ extern "C" int qrw_sim_set_host(qrw_handle h, const double* h_state) {
   HIP_OK(h2d(h, h->sim_st.p, h_state, h->sim_st.bytes), "qrw_sim_set_host: H2D simulator state");
   HIP_OK(host_done(h), "qrw_sim_set_host: H2D simulator state");
   note_launch(h, kFamSim, h->host_stream);
+  return 0;
+}
+
+// ---- heightfield terrain of the simulator
+static const char* sim_bad_terrain(const double* heights, int32_t rows, int32_t cols, double x0, double y0, double dx, double dy) {
+  if (!heights) return "null heights";
+  if (rows < 2 || cols < 2) return "rows and cols must be >= 2";
+  if (!(dx > 0.0) || !(dy > 0.0) || !std::isfinite(dx) || !std::isfinite(dy)) return "dx and dy must be positive and finite";
+  if (!std::isfinite(x0) || !std::isfinite(y0)) return "x0 and y0 must be finite";
+  return nullptr;
+}
+// The handle's own copy of the field (and of the origins), `kind` the direction of the copies on `stream`.  The buffers are
+// reallocated only when the size changes (hipFree waits for the device, so no launch still reads what goes); the setting takes
+// effect only once both copies are queued.
+static int sim_store_terrain(qrw_handle h, const char* who, const double* heights, int32_t rows, int32_t cols, double x0, double y0,
+                             double dx, double dy, const double* origin_xy, hipMemcpyKind kind, hipStream_t stream) {
+  const size_t count = (size_t)rows * (size_t)cols, B = (size_t)h->cfg.batch;
+  if (h->sim_terrain.count() != count) {
+    h->sim_terrain_on = false;
+    HIP_OK(h->sim_terrain.alloc(count), who);
+  }
+  if (origin_xy && h->sim_origin.count() != 2 * B) {
+    h->sim_origin_on = false;
+    HIP_OK(h->sim_origin.alloc(2 * B), who);
+  }
+  HIP_OK(hipMemcpyAsync(h->sim_terrain.p, heights, h->sim_terrain.bytes, kind, stream), who);
+  if (origin_xy) HIP_OK(hipMemcpyAsync(h->sim_origin.p, origin_xy, h->sim_origin.bytes, kind, stream), who);
+  h->sim_t_rows = rows; h->sim_t_cols = cols;
+  h->sim_t_x0 = x0; h->sim_t_y0 = y0; h->sim_t_dx = dx; h->sim_t_dy = dy;
+  h->sim_terrain_on = true;
+  h->sim_origin_on = origin_xy != nullptr;
+  note_launch(h, kFamSim, stream);
+  return 0;
+}
+
+extern "C" int qrw_sim_set_terrain(qrw_handle h, const double* d_heights, int32_t rows, int32_t cols, double x0, double y0, double dx,
+                                   double dy, const double* d_origin_xy, void* stream) {
+  QRW_ENTER(h, false, "qrw_sim_set_terrain: null handle");
+  if (const char* bad = sim_bad_terrain(d_heights, rows, cols, x0, y0, dx, dy))
+    return fail(-1, (std::string("qrw_sim_set_terrain: ") + bad).c_str());
+  return sim_store_terrain(h, "qrw_sim_set_terrain", d_heights, rows, cols, x0, y0, dx, dy, d_origin_xy, hipMemcpyDeviceToDevice,
+                           (hipStream_t)stream);
+}
+
+extern "C" int qrw_sim_set_terrain_host(qrw_handle h, const double* h_heights, int32_t rows, int32_t cols, double x0, double y0,
+                                        double dx, double dy, const double* h_origin_xy) {
+  QRW_ENTER_HOST(h, false, "qrw_sim_set_terrain_host: null handle");
+  if (const char* bad = sim_bad_terrain(h_heights, rows, cols, x0, y0, dx, dy))
+    return fail(-1, (std::string("qrw_sim_set_terrain_host: ") + bad).c_str());
+  HIP_OK(wait_family(h, kFamSim), "qrw_sim_set_terrain_host: earlier simulator step of this handle");
+  if (const int rc = sim_store_terrain(h, "qrw_sim_set_terrain_host", h_heights, rows, cols, x0, y0, dx, dy, h_origin_xy,
+                                       hipMemcpyHostToDevice, h->host_stream))
+    return rc;
+  HIP_OK(host_done(h), "qrw_sim_set_terrain_host: H2D terrain");
+  return 0;
+}
+
+extern "C" int qrw_sim_clear_terrain(qrw_handle h) {
+  if (!h) return fail(-1, "qrw_sim_clear_terrain: null handle");
+  h->sim_terrain_on = h->sim_origin_on = false;  // (the buffers stay for the next qrw_sim_set_terrain of the same size)
   return 0;
 }
 

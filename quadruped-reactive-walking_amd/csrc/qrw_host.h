@@ -124,6 +124,12 @@ struct qrw_handle_s {
   DevBuf<double> sim_st, sim_out;
   qrw_sim_params sim_prm;
   bool sim_ready = false;
+  // the simulator's heightfield terrain (qrw_sim_set_terrain): the handle's own copy of the heights and of the per-robot
+  // origins, kept across qrw_sim_init; the buffers are reallocated only when their size changes
+  DevBuf<double> sim_terrain, sim_origin;
+  int sim_t_rows = 0, sim_t_cols = 0;
+  double sim_t_x0 = 0.0, sim_t_y0 = 0.0, sim_t_dx = 0.0, sim_t_dy = 0.0;
+  bool sim_terrain_on = false, sim_origin_on = false;
   // staging for the host-buffer entry points
   DevBuf<double> stage;
   DevBuf<int32_t> stage_i;
@@ -213,6 +219,15 @@ struct HostStreamGuard {
 #define QRW_ENTER_HOST(h, bad, what) \
   QRW_ENTER(h, bad, what);           \
   qrw::host::HostStreamGuard host_guard__(h)
+
+// the handle's terrain into a simulator launch (none set: the arguments stay zero and sim_launch picks the flat instantiation)
+inline void sim_terrain_args(const qrw_handle_s* h, qrw::SimArgs& a) {
+  if (!h->sim_terrain_on) return;
+  a.terrain = h->sim_terrain;
+  a.t_rows = h->sim_t_rows; a.t_cols = h->sim_t_cols;
+  a.t_x0 = h->sim_t_x0; a.t_y0 = h->sim_t_y0; a.t_dx = h->sim_t_dx; a.t_dy = h->sim_t_dy;
+  a.t_origin = h->sim_origin_on ? h->sim_origin.p : nullptr;
+}
 
 // the launch form qrw_mpc_solve uses for this handle (decided once, at creation)
 inline bool mpc_time_sliced(const qrw_handle_s* h) { return h->pre_chunk > 0 && h->cfg.batch > h->pre_min_batch && h->pre_cmax > 1; }

@@ -242,6 +242,11 @@ struct SimArgs {
   double *contact_forces, *joint_torques;          // [B][4][3] world, [B][12]
   const double *fd_q, *fd_v, *fd_tau;              // mode 2: [B][19], [B][18], [B][12]
   double* fd_a;                                    // mode 2: [B][18]
+  // heightfield terrain, or terrain null for the plane z = 0 (sim_terrain.h: [rows][cols], vertex (r, c) at x0 + c dx, y0 + r dy)
+  const double* terrain;
+  int t_rows, t_cols;
+  double t_x0, t_y0, t_dx, t_dy;
+  const double* t_origin;                          // [B][2] per-robot offset of the query point, or null
 };
 int sim_launch(const SimArgs& a, hipStream_t stream);
 }

@@ -264,6 +264,9 @@ extern "C" int qrw_test_sim_forward_dynamics(qrw_handle h, int32_t n, const doub
     return fail(-1, "qrw_test_sim_forward_dynamics: bad argument");
   DeviceScope dev_scope__(h->cfg.device);
   const size_t N = (size_t)n;
+  // the handle's terrain is used as in the other modes; its per-robot origins hold one row per instance of the handle's batch
+  if (h->sim_terrain_on && h->sim_origin_on && n > h->cfg.batch)
+    return fail(-1, "qrw_test_sim_forward_dynamics: more states than the terrain's per-robot origins (the handle's batch)");
   DevBuf<double> q, v, tau, fe, a18, cf;
   HIP_OK(q.alloc(N * 19), "qrw_test_sim_forward_dynamics alloc");
   HIP_OK(v.alloc(N * 18), "qrw_test_sim_forward_dynamics alloc");
@@ -282,6 +285,8 @@ extern "C" int qrw_test_sim_forward_dynamics(qrw_handle h, int32_t n, const doub
   a.B = n; a.mode = 2; a.substeps = 1; a.dt = params->dt;
   a.kn = params->kn; a.dn = params->dn; a.mu = params->mu; a.vs = params->vs; a.foot_radius = params->foot_radius;
   a.fd_q = q; a.fd_v = v; a.fd_tau = tau; a.f_ext = h_f_ext ? fe.p : nullptr; a.fd_a = a18; a.contact_forces = cf;
+  HIP_OK(wait_family(h, kFamSim), "qrw_test_sim_forward_dynamics: earlier simulator work of this handle");  // (a terrain copy in flight)
+  sim_terrain_args(h, a);
   if (qrw::sim_launch(a, h->host_stream) != 0) return fail(-11, "qrw_test_sim_forward_dynamics: launch failed", hipGetLastError());
   HIP_OK(hipStreamSynchronize(h->host_stream), "qrw_test_sim_forward_dynamics");
   HIP_OK(hipMemcpy(h_a18, a18, a18.bytes, hipMemcpyDeviceToHost), "qrw_test_sim_forward_dynamics D2H");

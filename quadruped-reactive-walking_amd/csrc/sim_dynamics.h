@@ -11,6 +11,7 @@
 // block's inverse and a Schur complement onto the base's 6x6; the four legs' contributions are summed by the caller
 // (DPP quad sums on the device).
 #pragma once
+#include "sim_terrain.h"
 #include "solo12_leg.h"
 
 namespace qrw {
@@ -86,6 +87,29 @@ struct SimContact {
   double kn, dn, mu, vs, foot_radius;
 };
 
+// The ground of the terrain instantiation: one heightfield for the whole batch (sim_terrain.h) and this robot's offset into it
+// (the foot at world (x, y) is looked up at (x + ox, y + oy); zero when the caller gave no origins).
+struct SimGround {
+  terrain::Field T;
+  double ox, oy;
+};
+
+// Contact of one foot (centre at height z_foot, world velocity v) with the triangle's plane s under it: with the unit normal
+// n = (-gx, -gy, 1)/|.|, d = foot_radius - n_z (z_foot - h) is how far the foot's sphere reaches through the plane, the normal
+// force kn d - dn (n.v) clipped at 0 while d > 0, regularised Coulomb friction against the tangential velocity v - (n.v) n.
+// For a field of zeros this is the plane z = 0's formula term by term (n = (-0, -0, 1)).
+__device__ __forceinline__ V3 sim_terrain_force(const terrain::Plane& s, double z_foot, V3 v, const SimContact& cp) {
+  const double in = 1.0 / sqrt(s.gx * s.gx + s.gy * s.gy + 1.0);
+  const V3 n = mk(-s.gx * in, -s.gy * in, in);
+  const double d = cp.foot_radius - n.z * (z_foot - s.h);
+  const double vn = dot(n, v);
+  double fn = 0.0;
+  if (d > 0.0) fn = fmax(0.0, cp.kn * d - cp.dn * vn);
+  const V3 vt = v - vn * n;
+  const double kt = -cp.mu * fn / sqrt(dot(vt, vt) + cp.vs * cp.vs);
+  return fn * n + kt * vt;
+}
+
 // What one leg adds to the base's 6x6 system, and what it keeps to recover its own joint accelerations.
 struct LegPart {
   double S[21];    // upper triangle (row-major) of: the leg's composite inertia minus F H^-1 F'
@@ -97,22 +121,37 @@ struct LegPart {
 };
 
 // One leg at (q3, dq3) under the torques tau3, hanging from a base with rotation R (world <- base), height of its origin pz
-// and velocity (vb, wb) in the base frame.
+// and velocity (vb, wb) in the base frame.  kTerrain: the ground is the heightfield g under the base at (px, py) instead of the
+// plane z = 0 (px, py and g are not read otherwise).
+template <bool kTerrain>
 __device__ __forceinline__ LegPart sim_leg_part(int j, const double q3[3], const double dq3[3], const double tau3[3], const M3& R,
-                                                double pz, V3 vb, V3 wb, const SimContact& cp) {
+                                                double px, double py, double pz, V3 vb, V3 wb, const SimContact& cp, const SimGround& g) {
   LegPart P;
   const LegC C = leg_consts(j);
   const LegKin K = leg_kinematics(C, q3);
-  // ---- contact: penalty normal force on the plane z = 0, regularised Coulomb friction
+  // ---- contact: penalty normal force on the plane z = 0 (or the heightfield), regularised Coulomb friction
   const V3 v_foot_b = vb + cross(wb, K.pf) + dq3[0] * K.J0 + dq3[1] * K.J1 + dq3[2] * K.J2;
   const V3 v_foot = mul(R, v_foot_b);
   const double z_foot = pz + dot(R.r2, K.pf);
-  const double d = cp.foot_radius - z_foot;
-  double fn = 0.0;
-  if (d > 0.0) fn = fmax(0.0, cp.kn * d - cp.dn * v_foot.z);
-  const double kt = -cp.mu * fn / sqrt(v_foot.x * v_foot.x + v_foot.y * v_foot.y + cp.vs * cp.vs);
-  P.f_world = mk(kt * v_foot.x, kt * v_foot.y, fn);
-  const V3 fb = mulT(R, P.f_world);
+  terrain::Axis cu, cv;
+  terrain::Corners hc;
+  V3 fb;  // the contact force in the base frame
+  if constexpr (kTerrain) {
+    // the cell under the foot and its four heights (two 16-byte loads): the tick's only new memory traffic, asked for here, as soon
+    // as the foot's position is known; the force is formed after the bodies and the bias pass.  (How much of that arithmetic the
+    // compiler really leaves between the loads and their wait, at 256 VGPRs, is recorded in DESIGN.md 4.7.)
+    cu = terrain::axis_cell(px + dot(R.r0, K.pf) + g.ox, g.T.x0, g.T.dx, g.T.cols);
+    cv = terrain::axis_cell(py + dot(R.r1, K.pf) + g.oy, g.T.y0, g.T.dy, g.T.rows);
+    hc = terrain::load_corners(g.T, cv.i, cu.i);
+    __builtin_amdgcn_sched_barrier(0);  // (keeps the loads here, ahead of what follows; without it: 212 AGPRs and 6 spilled registers)
+  } else {
+    const double d = cp.foot_radius - z_foot;
+    double fn = 0.0;
+    if (d > 0.0) fn = fmax(0.0, cp.kn * d - cp.dn * v_foot.z);
+    const double kt = -cp.mu * fn / sqrt(v_foot.x * v_foot.x + v_foot.y * v_foot.y + cp.vs * cp.vs);
+    P.f_world = mk(kt * v_foot.x, kt * v_foot.y, fn);
+    fb = mulT(R, P.f_world);
+  }
   // ---- bodies and joints
   const RB b0 = rb_of(C.m[0], C.com[0], C.I[0], K.R0, K.p0);
   const RB b1 = rb_of(C.m[1], C.com[1], C.I[1], K.R1, K.p1);
@@ -132,6 +171,11 @@ __device__ __forceinline__ LegPart sim_leg_part(int j, const double q3[3], const
   const SV f3 = rb_force(b2, v3, a3);
   const SV f2 = rb_force(b1, v2, a2) + f3;
   const SV f1 = rb_force(b0, v1, a1) + f2;
+  if constexpr (kTerrain) {
+    __builtin_amdgcn_sched_barrier(0);
+    P.f_world = sim_terrain_force(terrain::plane_of(hc, cu.f, cv.f, g.T.dx, g.T.dy), z_foot, v_foot, cp);
+    fb = mulT(R, P.f_world);
+  }
   // ---- right-hand sides
   P.rj[0] = tau3[0] + dot(K.J0, fb) - sdot(S0, f1);
   P.rj[1] = tau3[1] + dot(K.J1, fb) - sdot(S1, f2);

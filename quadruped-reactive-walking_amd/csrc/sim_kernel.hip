@@ -4,14 +4,18 @@
 //   SendCommand       :672-710  the PD+ law from the joint state at the start of the tick (:679-688), then the physics step
 //   UpdateMeasurment  :588-633  the readings the estimator takes (qrw_estimator_step reads these buffers as they are written)
 // The physics step is NOT PyBullet's: `substeps` semi-implicit Euler steps of the forward dynamics M(q) a = [0; tau] + J'f +
-// external wrench - h(q, v) (sim_dynamics.h) with a penalty normal force and regularised Coulomb friction on the plane z = 0.
-// No joint limits, no joint friction, no other terrain; nothing about PyBullet's numerics is reproduced or claimed.
+// external wrench - h(q, v) (sim_dynamics.h) with a penalty normal force and regularised Coulomb friction on the plane z = 0 or,
+// in the kernel's second instantiation, on a triangulated heightfield shared by the batch (sim_terrain.h; each robot may look
+// it up at an offset of its own).  No joint limits, no joint friction; nothing about PyBullet's numerics is reproduced or claimed.
 //
 // Mapping: lane = 4*instance_in_wave + leg (FL, FR, HL, HR), ONE QUAD PER ROBOT INSTANCE, 16 instances per wavefront -- the
 // mapping of estimator_kernel.  Each lane works its own leg: kinematics, contact force, bias forces, its 3x3 block of the
 // mass matrix and the Schur complement of that block onto the base.  The four legs' shares of the base's 6x6 system (21 + 6
 // numbers) go through DPP quad sums; all four lanes then solve the 6x6 alike, integrate the base alike and share the stores.
-// No LDS.  The persistent state is item-major ([item][B]).
+// No LDS.  The persistent state is item-major ([item][B]).  The heightfield is read straight from global memory, four heights
+// per lane and sub-step (two 16-byte loads) with no reuse across lanes (a 512 x 512 field is 2 MiB and stays in the L2); they are
+// asked for as soon as the foot's position is known (sim_leg_part; what the compiler makes of that at 256 VGPRs: DESIGN.md 4.7).
+// sim_kernel<false> is, instruction for instruction, the kernel from before there was a terrain.
 //
 // A robot whose new state is not finite sets its status item and is frozen: no state item and no output of that tick or
 // any later one is stored (the buffers keep what the last finite tick wrote); its quad leaves at once on later ticks.
@@ -31,9 +35,11 @@ __device__ __forceinline__ double pick3(V3 v, int j) { return j == 0 ? v.x : j =
 __device__ __forceinline__ bool finite3(V3 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
 
 // the acceleration of (q, v) under tau for this lane's leg and the base: the quad's four lanes call it together
-__device__ __forceinline__ void sim_accel(int j, const double q3[3], const double dq3[3], const double tau3[3], const M3& R, double pz,
-                                          V3 vb, V3 wb, V3 fe, V3 me, const SimContact& cp, double ab[6], double ddq[3], V3& f_world) {
-  const LegPart P = sim_leg_part(j, q3, dq3, tau3, R, pz, vb, wb, cp);
+template <bool kTerrain>
+__device__ __forceinline__ void sim_accel(int j, const double q3[3], const double dq3[3], const double tau3[3], const M3& R, double px,
+                                          double py, double pz, V3 vb, V3 wb, V3 fe, V3 me, const SimContact& cp, const SimGround& g,
+                                          double ab[6], double ddq[3], V3& f_world) {
+  const LegPart P = sim_leg_part<kTerrain>(j, q3, dq3, tau3, R, px, py, pz, vb, wb, cp, g);
   double S[21], r[6];
 #pragma unroll
   for (int e = 0; e < 21; e++) S[e] = quad_sum(P.S[e]);
@@ -47,6 +53,7 @@ __device__ __forceinline__ void sim_accel(int j, const double q3[3], const doubl
 
 }  // namespace
 
+template <bool kTerrain>
 __global__ __launch_bounds__(64) void sim_kernel(SimArgs a) {
   const int t = blockIdx.x * 64 + threadIdx.x;
   const int b = t >> 2, j = t & 3;
@@ -59,6 +66,14 @@ __global__ __launch_bounds__(64) void sim_kernel(SimArgs a) {
     const double* f = a.f_ext + (size_t)b * 6;
     fe = mk(f[0], f[1], f[2]);
     me = mk(f[3], f[4], f[5]);
+  }
+  SimGround g{};
+  if constexpr (kTerrain) {
+    g.T = terrain::Field{a.terrain, a.t_rows, a.t_cols, a.t_x0, a.t_y0, a.t_dx, a.t_dy};
+    if (a.t_origin) {
+      g.ox = a.t_origin[(size_t)b * 2];
+      g.oy = a.t_origin[(size_t)b * 2 + 1];
+    }
   }
 
   if (a.mode == 2) {  // forward dynamics only (tests): a18 and the contact forces of the given state
@@ -73,7 +88,7 @@ __global__ __launch_bounds__(64) void sim_kernel(SimArgs a) {
     }
     const M3 R = sim_quat_to_rot(q[3], q[4], q[5], q[6]);
     V3 fw;
-    sim_accel(j, q3, dq3, tau3, R, q[2], mk(v[0], v[1], v[2]), mk(v[3], v[4], v[5]), fe, me, cp, ab, ddq, fw);
+    sim_accel<kTerrain>(j, q3, dq3, tau3, R, q[0], q[1], q[2], mk(v[0], v[1], v[2]), mk(v[3], v[4], v[5]), fe, me, cp, g, ab, ddq, fw);
     double* o = a.fd_a + (size_t)b * 18;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -106,6 +121,13 @@ __global__ __launch_bounds__(64) void sim_kernel(SimArgs a) {
       q3[i] = q[3 * j + i];
       dq3[i] = 0.0;
     }
+    if constexpr (kTerrain) {
+      // the joints alone: the level base at (0, 0) stands base_height above the highest ground under its four feet
+      if (a.q_ld != 19) {
+        const V3 pf = leg_kinematics(leg_consts(j), q3).pf;
+        p[2] += quad_max(terrain::surface(g.T, pf.x + g.ox, pf.y + g.oy).h);
+      }
+    }
     vb = wb = prev = mk(0.0, 0.0, 0.0);
   } else {
     if (s[(size_t)kSsStatus * B] != 0.0) return;  // frozen (the whole quad reads the same word)
@@ -135,7 +157,7 @@ __global__ __launch_bounds__(64) void sim_kernel(SimArgs a) {
     for (int k = 0; k < a.substeps; k++) {
       const M3 R = sim_quat_to_rot(quat[0], quat[1], quat[2], quat[3]);
       double ab[6], ddq[3];
-      sim_accel(j, q3, dq3, tau3, R, p[2], vb, wb, fe, me, cp, ab, ddq, fw);
+      sim_accel<kTerrain>(j, q3, dq3, tau3, R, p[0], p[1], p[2], vb, wb, fe, me, cp, g, ab, ddq, fw);
       // semi-implicit Euler: velocities first, positions from the new velocities
       vb = vb + h * mk(ab[0], ab[1], ab[2]);
       wb = wb + h * mk(ab[3], ab[4], ab[5]);
@@ -197,7 +219,8 @@ __global__ __launch_bounds__(64) void sim_kernel(SimArgs a) {
 }
 
 int sim_launch(const SimArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL(sim_kernel, dim3((a.B + 15) / 16), dim3(64), 0, stream, a);
+  if (a.terrain) hipLaunchKernelGGL(sim_kernel<true>, dim3((a.B + 15) / 16), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(sim_kernel<false>, dim3((a.B + 15) / 16), dim3(64), 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

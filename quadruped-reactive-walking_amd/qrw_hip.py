@@ -151,6 +151,9 @@ SIGNATURES = {
     "qrw_sim_step_host": (C.c_int, [_vp] + [_dp] * 6 + [C.POINTER(_SimBuffers)]),
     "qrw_sim_get_host": (C.c_int, [_vp, _dp]),
     "qrw_sim_set_host": (C.c_int, [_vp, _dp]),
+    "qrw_sim_set_terrain": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32] + [C.c_double] * 4 + [_vp, _vp]),
+    "qrw_sim_set_terrain_host": (C.c_int, [_vp, _dp, C.c_int32, C.c_int32] + [C.c_double] * 4 + [_dp]),
+    "qrw_sim_clear_terrain": (C.c_int, [_vp]),
     "qrw_stream_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
     "qrw_stream_destroy": (C.c_int, [_vp]),
     "qrw_device_cu_count": (C.c_int, [C.c_int32, _ip]),
@@ -809,6 +812,31 @@ class Batch:
         st[:, :19], st[:, 19:37], st[:, 37:40] = _h(q, (self.B, 19)), _h(v, (self.B, 18)), _h(prev_o_imuVel, (self.B, 3))
         st[:, 40], st[:, 41] = tick, status
         _check(self._lib.qrw_sim_set_host(self._handle, _p(np.ascontiguousarray(st.T))), "qrw_sim_set_host")
+
+    def sim_set_terrain(self, heights, dx, dy, x0=0.0, y0=0.0, origin=None):
+        """qrw_sim_set_terrain: one heightfield for all robots of this handle, heights (rows, cols) with vertex (r, c) at
+        x = x0 + c dx, y = y0 + r dy; origin (B,2) or None: robot b looks the field up at (x + origin[b,0], y + origin[b,1]).
+        CUDA float64 tensors are copied device-to-device on the current stream; numpy arrays (both, then) go through
+        qrw_sim_set_terrain_host, synchronised per handle.  The handle keeps its own copy; it survives sim_init."""
+        geo = (float(x0), float(y0), float(dx), float(dy))
+        if isinstance(heights, np.ndarray) or isinstance(heights, (list, tuple)):
+            hts = np.ascontiguousarray(np.asarray(heights, dtype=np.float64))
+            if hts.ndim != 2:
+                raise QrwError("heights must be (rows, cols)")
+            org = None if origin is None else _h(np.asarray(origin, dtype=np.float64), (self.B, 2))
+            _check(self._lib.qrw_sim_set_terrain_host(self._handle, _p(hts), hts.shape[0], hts.shape[1], *geo, _p(org)),
+                   "qrw_sim_set_terrain_host")
+            return
+        if heights.dim() != 2:
+            raise QrwError("heights must be (rows, cols)")
+        rows, cols = int(heights.shape[0]), int(heights.shape[1])
+        org = _vp(0) if origin is None else self._dev(origin, (self.B, 2))
+        _check(self._lib.qrw_sim_set_terrain(self._handle, self._dev(heights, (rows, cols)), rows, cols, *geo, org, self._stream()),
+               "qrw_sim_set_terrain")
+
+    def sim_clear_terrain(self):
+        """qrw_sim_clear_terrain: back to the plane z = 0."""
+        _check(self._lib.qrw_sim_clear_terrain(self._handle), "qrw_sim_clear_terrain")
 
     def test_sim_forward_dynamics(self, q19, v18, tau12, f_ext=None, **params):
         """Tests only (qrw_test_sim_forward_dynamics): a18 (n,18) and the contact forces (n,4,3) of n states."""

@@ -11,7 +11,15 @@ Batch 4096 and 256, one process, the four legs alternating round by round (>= 20
 Two figures per leg, microseconds per call, as scripts/gpu_estimator_timing.py takes them: `device` = the calls queued behind a
 blocker kernel and timed by two events once it ends; `issued` = the same calls timed while the host issues them.
 The simulated robots hold the stance under P = 3, D = 0.2 and are re-initialised before every timed window (outside it); `frozen`
-counts robots whose status was set in a window -- a frozen robot's quad leaves early, so a figure with frozen robots is too low."""
+counts robots whose status was set in a window -- a frozen robot's quad leaves early, so a figure with frozen robots is too low.
+
+    python scripts/gpu_sim_timing.py --terrain [rounds=10] [calls=200]          ->  profiles/sim_terrain_timing.json
+
+The two instantiations of sim_kernel side by side, by the same method: `flat` = qrw_sim_step (8 sub-steps) on a handle without a
+terrain, `terrain` = the same on a second handle that holds the reference's rough ground (Simulator.reference_rough_ground, 512 x
+512) with one origin per robot on a grid over the field, so that the fleet's height loads spread over the whole 2 MiB.  The two
+legs alternate round by round in one process, at batch 4096 and 256.  The flat figure is the one to hold against
+profiles/sim_timing.json (sim_step_8): that file's run-to-run spread is its min..max."""
 import ctypes as C
 import json
 import os
@@ -26,14 +34,16 @@ import qrw_hip  # noqa: E402
 import synth  # noqa: E402
 from Controller import Controller_batch  # noqa: E402
 
-ROUNDS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-CALLS = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+TERRAIN = "--terrain" in sys.argv
+ARGV = [a for a in sys.argv if a != "--terrain"]
+ROUNDS = int(ARGV[1]) if len(ARGV) > 1 else 10
+CALLS = int(ARGV[2]) if len(ARGV) > 2 else 200
 Q_INIT = np.array([0.0, 0.7, -1.4, -0.0, 0.7, -1.4, 0.0, -0.7, +1.4, -0.0, -0.7, +1.4])
 LEGS = ("sim_step_8", "sim_step_1", "control_pre", "iteration")
 
 
 def sim_leg(b, substeps, dev):
-    """(tick, reset, frozen) on handle b: argument-free callables on fixed buffers."""
+    """(tick, reset, frozen) on handle b (whatever terrain it holds): argument-free callables on fixed buffers."""
     B = b.B
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     q0, out = t(np.tile(Q_INIT, (B, 1))), b.sim_outputs()
@@ -133,5 +143,50 @@ def main():
     json.dump(out, open(os.path.join(ROOT, "profiles", "sim_timing.json"), "w"), indent=1, sort_keys=True)
 
 
+def main_terrain():
+    assert torch.cuda.is_available(), "needs a GPU"
+    from Simulator import reference_rough_ground
+
+    dev = torch.device("cuda", 0)
+    ground = reference_rough_ground()
+    legs = ("flat", "terrain")
+    out = {"rounds": ROUNDS, "calls_per_round": CALLS, "unit": "us per call", "substeps": 8,
+           "field": "reference_rough_ground(): 512 x 512, 0.05 m, one origin per robot on a grid", "batches": {}}
+    with torch.cuda.stream(torch.cuda.Stream(dev)):
+        for B in (4096, 256):
+            side = int(np.ceil(np.sqrt(B)))
+            at = np.linspace(ground["x0"] + 2.0, -ground["x0"] - 2.0, side)
+            origin = np.stack(np.meshgrid(at, at), axis=-1).reshape(-1, 2)[:B].copy()
+            flat, rough = qrw_hip.Batch(B), qrw_hip.Batch(B)
+            rough.sim_set_terrain(ground["heights"], ground["dx"], ground["dy"], x0=ground["x0"], y0=ground["y0"], origin=origin)
+            leg = {"flat": sim_leg(flat, 8, dev), "terrain": sim_leg(rough, 8, dev)}
+            for name in legs:
+                timed(leg[name][0], CALLS, False)
+            rec = {name: {"device": [], "issued": []} for name in legs}
+            stuck = {name: 0 for name in legs}
+            for _ in range(ROUNDS):
+                for kind, blocked in (("device", True), ("issued", False)):
+                    for name in legs:
+                        tick, reset, frozen, _ = leg[name]
+                        reset()
+                        torch.cuda.current_stream().synchronize()
+                        rec[name][kind].append(timed(tick, CALLS, blocked))
+                        stuck[name] = max(stuck[name], frozen())
+            res = {name: {kind: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+                          for kind, v in kinds.items()} for name, kinds in rec.items()}
+            for name in legs:
+                res[name]["frozen"] = stuck[name]
+            res["terrain_over_flat"] = res["terrain"]["device"]["median"] / res["flat"]["device"]["median"]
+            ref = os.path.join(ROOT, "profiles", "sim_timing.json")
+            if os.path.exists(ref):  # the flat figure of the commit before the terrain, and that file's own spread
+                was = json.load(open(ref))["batches"][str(B)]["sim_step_8"]["device"]
+                res["flat_recorded_before"] = was
+                res["flat_over_recorded"] = res["flat"]["device"]["median"] / was["median"]
+            out["batches"][str(B)] = res
+            print(B, json.dumps(res))
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    json.dump(out, open(os.path.join(ROOT, "profiles", "sim_terrain_timing.json"), "w"), indent=1, sort_keys=True)
+
+
 if __name__ == "__main__":
-    main()
+    main_terrain() if TERRAIN else main()

@@ -1,0 +1,24 @@
+#!/usr/bin/env python3
+"""The terrain tests' tolerances as measured (no GPU; the sibling of scripts/sim_tolerance.py): the numpy checker
+tests/sim_terrain_numpy.py held against itself on the states of tests/test_gpu_sim_terrain.py with every input moved by one ulp.
+Prints the spreads behind FD_SPREAD / TICK_SPREAD there, and how near the checker's free run of the teacher-forced case comes to
+the switches of the contact law (d = 0, the diagonal fu = fv, the cell edges), the numbers of feet in contact and the triangle
+kinds it sees."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "quadruped-reactive-walking_amd")]
+import oracle  # noqa: E402
+
+oracle.build()
+import sim_terrain_numpy as stn  # noqa: E402
+import test_gpu_sim_terrain as t  # noqa: E402
+
+solve, ulp = t.fd_spread(stn)
+print("forward dynamics on terrain: float64 vs longdouble solve %.3g, inputs moved by one ulp %.3g (FD_SPREAD %.3g, FD_BOUND %.3g)"
+      % (solve, ulp, t.FD_SPREAD, t.FD_BOUND))
+spread, d_min, diag_min, edge_min, seen, kinds = t.tick_spread(stn)
+print("one tick on the rough field: state moved by one ulp %.3g (TICK_SPREAD %.3g, TICK_BOUND %.3g); smallest |d| %.3g, "
+      "|fu - fv| %.3g, distance of fu, fv to a cell edge %.3g; feet in contact seen %s, triangles %s"
+      % (spread, t.TICK_SPREAD, t.TICK_BOUND, d_min, diag_min, edge_min, sorted(seen), sorted(kinds)))
