@@ -416,7 +416,9 @@ typedef struct {
 /* Sets the state (d_q_init [B][q_ld]: q_ld = 19 the whole q19, q_ld = 12 the joints with the base level at params->base_height
  * (above the highest ground under its feet when a terrain is set);
  * velocities, prev_o_imuVel, tick and status zero) and writes the first measurement, as the reference's first UpdateMeasurment.
- * Again = re-initialise. */
+ * Again = re-initialise: every robot whose d_q_init is finite starts afresh with status 0, whatever its status was.  A robot
+ * whose d_q_init is not finite gets status 1 and nothing else of it is stored: its other state items and its rows of the output
+ * buffers keep what they held (the state zero in a handle that was never initialised before); the others are unaffected. */
 int qrw_sim_init(qrw_handle h, const double *d_q_init, int32_t q_ld, const qrw_sim_params *params, const qrw_sim_buffers *out,
                  void *stream);
 /* One tick.  d_P, d_D, d_q_des, d_v_des, d_tau_ff: rows of 12 per instance, cmd_ld doubles apart (12 for five plain [B][12]
@@ -431,7 +433,7 @@ int qrw_sim_init_host(qrw_handle h, const double *h_q_init, int32_t q_ld, const 
 int qrw_sim_step_host(qrw_handle h, const double *h_P, const double *h_D, const double *h_q_des, const double *h_v_des,
                       const double *h_tau_ff, const double *h_f_ext, const qrw_sim_buffers *h_out);
 /* The whole state, [QRW_SIM_STATE_ITEMS][batch] (item-major, as the device holds it): for tests and restarts.  Setting it does
- * not rewrite the measurement buffers. */
+ * not rewrite the measurement buffers.  A frozen robot given a finite state and status 0 steps again from the next tick on. */
 int qrw_sim_get_host(qrw_handle h, double *h_state);
 int qrw_sim_set_host(qrw_handle h, const double *h_state);
 

@@ -3,7 +3,7 @@
 tests/sim_terrain_numpy.py held against itself on the states of tests/test_gpu_sim_terrain.py with every input moved by one ulp.
 Prints the spreads behind FD_SPREAD / TICK_SPREAD there, and how near the checker's free run of the teacher-forced case comes to
 the switches of the contact law (d = 0, the diagonal fu = fv, the cell edges), the numbers of feet in contact and the triangle
-kinds it sees."""
+kinds it sees.  Then the same for the rough field's cases of tests/test_gpu_sim_params.py (every parameter changed)."""
 import os
 import sys
 
@@ -22,3 +22,13 @@ spread, d_min, diag_min, edge_min, seen, kinds = t.tick_spread(stn)
 print("one tick on the rough field: state moved by one ulp %.3g (TICK_SPREAD %.3g, TICK_BOUND %.3g); smallest |d| %.3g, "
       "|fu - fv| %.3g, distance of fu, fv to a cell edge %.3g; feet in contact seen %s, triangles %s"
       % (spread, t.TICK_SPREAD, t.TICK_BOUND, d_min, diag_min, edge_min, sorted(seen), sorted(kinds)))
+
+# tests/test_gpu_sim_params.py: the rough field's states and run, settled and run with every parameter changed
+import test_gpu_sim_params as tp  # noqa: E402
+
+ulp, (spread, d_min, diag_min, edge_min, seen, kinds) = tp.terrain_spreads(stn)
+print("forward dynamics on the rough field under TUNED: inputs moved by one ulp %.3g (T_FD_SPREAD %.3g, T_FD_BOUND %.3g)"
+      % (ulp, tp.T_FD_SPREAD, tp.T_FD_BOUND))
+print("one tick on the rough field under TUNED: state moved by one ulp %.3g (T_TICK_SPREAD %.3g, T_TICK_BOUND %.3g); smallest |d| "
+      "%.3g, |fu - fv| %.3g, distance of fu, fv to a cell edge %.3g; feet in contact seen %s, triangles %s"
+      % (spread, tp.T_TICK_SPREAD, tp.T_TICK_BOUND, d_min, diag_min, edge_min, sorted(seen), sorted(kinds)))

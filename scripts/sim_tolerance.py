@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The simulator tests' tolerances as measured (no GPU): the numpy checker tests/sim_numpy.py held against itself on the states
 of tests/test_gpu_sim.py.  Prints the spreads behind FD_SPREAD / TICK_SPREAD there, the smallest |d| of the checker's free run
-of the teacher-forced case (the contact law switches at d = 0) and the numbers of feet in contact that run sees."""
+of the teacher-forced case (the contact law switches at d = 0) and the numbers of feet in contact that run sees.  Then the same
+for the cases of tests/test_gpu_sim_params.py: every parameter changed at once, each contact parameter alone (with the change
+it makes to the accelerations), and five ticks at other sub-step counts and another dt."""
 import os
 import sys
 
@@ -16,3 +18,21 @@ print("forward dynamics: float64 vs longdouble solve %.3g, inputs moved by one u
 spread, smallest, seen = t.tick_spread(sn)
 print("one tick: state moved by one ulp %.3g (TICK_SPREAD %.3g, TICK_BOUND %.3g); smallest |d| %.3g; feet in contact seen %s"
       % (spread, t.TICK_SPREAD, t.TICK_BOUND, smallest, sorted(seen)))
+
+# tests/test_gpu_sim_params.py: the same states and the same run with the parameters changed
+import test_gpu_sim_params as tp  # noqa: E402
+
+fd, tick = tp.plane_spreads(sn)
+for case, ulp in fd.items():
+    print("forward dynamics, %s: inputs moved by one ulp %.3g" % (case if case == "TUNED" else case + " alone", ulp))
+print("  -> largest %.3g (FD_SPREAD %.3g, FD_BOUND %.3g in test_gpu_sim_params)" % (max(fd.values()), tp.FD_SPREAD, tp.FD_BOUND))
+for case, (spread, smallest, seen) in tick.items():
+    print("one tick, %s: state moved by one ulp %.3g; smallest |d| %.3g; feet in contact seen %s" % (case, spread, smallest, sorted(seen)))
+print("  -> TUNED %.3g (TICK_SPREAD %.3g, TICK_BOUND %.3g in test_gpu_sim_params); the largest of the five-tick cases %.3g "
+      "(V_TICK_SPREAD %.3g, V_TICK_BOUND %.3g)" % (tick["TUNED"][0], tp.TICK_SPREAD, tp.TICK_BOUND,
+                                                    max(s for c, (s, _, _) in tick.items() if c != "TUNED"), tp.V_TICK_SPREAD, tp.V_TICK_BOUND))
+states = t._fd_states(sn)
+a_def = [sn.forward_dynamics(q, v, tau)[0] for q, v, tau, _, _ in states]
+for name, value in tp.SINGLE.items():
+    a_one = [sn.forward_dynamics(q, v, tau, dict(sn.DEFAULTS, **{name: value}))[0] for q, v, tau, _, _ in states]
+    print("largest relative change in a over the 17 states, %s alone: %.3g" % (name, max(t._rel(x, y) for x, y in zip(a_one, a_def))))

@@ -111,6 +111,23 @@ def measurements(q19, v18, prev_o_imuVel, dt):
                 true_pos=q19[:3].copy(), true_b_vel=v18[:3].copy())  # dummyPos (:604), b_baseVel (:624)
 
 
+def world_momentum(q19, v18):
+    """Linear momentum and angular momentum about the world origin, both in the world frame (6,).  The top six rows of M(q) v are
+    the robot's momentum in the base frame, the angular part about the base origin: rotated by R and moved by p x."""
+    hb = (oracle.crba(q19) @ v18)[:6]
+    R = quat_to_rot(q19[3:7])
+    lin = R @ hb[:3]
+    return np.concatenate([lin, R @ hb[3:] + np.cross(q19[:3], lin)])
+
+
+def tumbling_state(rng, height=1.0):
+    """An airborne state far from the ground: random attitude and joints, base twist and joint speeds of a few rad/s."""
+    quat = rng.normal(size=4)
+    q = np.concatenate([0.2 * rng.normal(size=2), [height], quat / np.linalg.norm(quat), Q_STANCE + 0.3 * rng.normal(size=12)])
+    v = np.concatenate([rng.normal(size=3), 2.0 * rng.normal(size=3), 3.0 * rng.normal(size=12)])
+    return q, v
+
+
 class SimNumpy:
     """One robot.  state(): (q19, v18, prev_o_imuVel, tick, status)."""
 

@@ -34,11 +34,12 @@ def _close(got, ref, what):
     assert np.allclose(got, ref, rtol=RTOL, atol=ATOL), (what, np.abs(np.asarray(got) - np.asarray(ref)).max(), got, ref)
 
 
-def _compare(eng, out, refs, tick, items=True):
-    """The four outputs of every robot and (items) every getter item against the checker objects."""
+def _compare(eng, out, refs, tick, items=True, robots=None):
+    """The four outputs of every robot and (items) every getter item against the checker objects (robots: the instances of the
+    handle they stand for; None: 0, 1, ...)."""
     import qrw_hip
 
-    for b, r in enumerate(refs):
+    for b, r in enumerate(refs) if robots is None else zip(robots, refs):
         _close(out["q_filt"][b], r.q_filt, ("q_filt", tick, b))
         _close(out["v_filt"][b], r.v_filt, ("v_filt", tick, b))
         _close(out["rpy"][b], r.RPY, ("rpy", tick, b))
@@ -130,6 +131,60 @@ def test_run_on_the_handles_planner_state(oracle_mod, synth_mod, en):
         torch.cuda.synchronize()
         for b, p in enumerate(plan):
             p.step(k, q7[b], vref[b], vref[b], int(code[b]))
+
+
+# ------------------------------------------------------------------------------------------------ off the default configuration
+def test_other_time_step_and_gait_table_length(oracle_mod, synth_mod, en):
+    """dt_wbc = 0.001 and gait matrices of 26 rows (tests/test_gpu_controller.py's ALT_CFG), B = 17, 120 ticks, noisy sensors: the
+    filters' coefficients and integration step take the handle's dt, the scan for the end of the phase runs over 26 rows (robots
+    2 and 9 have no zero row, robots 5 and 16 have 26 equal rows: the scan ends at N_gait).  All outputs and every state item,
+    every tick.  And the time step matters: the checker at 0.002 gives another v_filt."""
+    import qrw_hip
+    import test_gpu_estimator_kalman as K
+
+    seq = K.alt_trot_sequence(synth_mod)
+    eng = qrw_hip.Batch(17, **K.ALT_HANDLE)
+    eng.estimator_init(H_INIT)
+    refs, plain = [en.Estimator(K.ALT_DT, H_INIT) for _ in range(17)], en.Estimator(DT, H_INIT)
+    seen = set()
+    for k, t in enumerate(seq):
+        _step(eng, refs, k, t["sensors"], t["gait"], t["goals"])
+        K.checker_step(plain, t, 0)
+        seen |= {r.remaining_steps for r in refs}
+    assert all(r.k_log == 120 for r in refs) and seen >= {K.ALT_N_GAIT, 8, 1}, seen
+    assert any(r.alpha < 0.98 for r in refs)
+    assert not np.allclose(plain.v_filt, refs[0].v_filt, rtol=1e3 * RTOL, atol=1e3 * ATOL)
+
+
+def test_other_configuration_on_the_handles_planner_state(oracle_mod, synth_mod, en):
+    """The same configuration with d_gait / d_goals NULL, B = 5, 60 ticks: the handle's planner (k_mpc = 20, T_gait = 0.40, 26-row
+    matrices as 64-bit column masks) stepped after the estimator, against oracle planners of that configuration."""
+    import torch
+
+    import qrw_hip
+    import test_gpu_estimator_kalman as K
+
+    B = 5
+    eng = qrw_hip.Batch(B, **K.ALT_HANDLE)
+    eng.planner_init(**K.ALT_OPTIONS["planner_init"])
+    eng.estimator_init(H_INIT)
+    refs = [en.Estimator(K.ALT_DT, H_INIT) for _ in range(B)]
+    pout = None
+    for k, t in enumerate(K.planner_sequence(oracle_mod, synth_mod, seed=18, **K.ALT_PLANNER)):
+        assert t["gait"].shape == (B, K.ALT_N_GAIT, 4)
+        _step(eng, refs, k, t["sensors"], t["gait"], t["goals"], planner=True)
+        q7, vref, code = t["plan"]
+        pout = eng.planner_step(k, _t(q7), _t(vref), _t(vref), _t(code, np.int32), out=pout)
+        torch.cuda.synchronize()
+
+
+def test_block_coverage(oracle_mod, synth_mod, en):
+    """test_gpu_estimator_kalman.block_coverage for the complementary filters: B = 83 against B = 17 bit for bit over 20 ticks, the
+    first tick of robots 64..82 (the init kernel's second block) against the checker."""
+    import test_gpu_estimator_kalman as K
+
+    K.block_coverage(synth_mod, False, lambda: en.Estimator(DT, H_INIT),
+                     lambda eng, out, refs, robots: _compare(eng, out, refs, 0, robots=robots))
 
 
 # ------------------------------------------------------------------------------------------------ hand-made corners

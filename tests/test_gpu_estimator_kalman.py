@@ -18,7 +18,8 @@ H_INIT = 0.22294615
 DT = 0.002
 N_GAIT = 20
 RTOL, ATOL = 1e-9, 1e-11
-# scripts/kalman_tolerance.py: (a) 4.2e-15, (b) 2.1e-13, (c) 4.3e-13 on sequences() -> 100 x 4.3e-13
+# scripts/kalman_tolerance.py: (a) 4.2e-15, (b) 2.1e-13, (c) 4.3e-13 on sequences() -> 100 x 4.3e-13.  The sequences at the other
+# time step and gait table length (alt_trot_b17, alt_planner) give 1.99e-13 and 1.26e-13 at the most: below, so the constant stays.
 KALMAN_BOUND = 4.3e-11
 EXACT = ("k_since_contact", "close_from_contact", "k_log")
 SENSOR_KEYS = ("lin_acc", "ang_vel", "quat", "q_mes", "v_mes")
@@ -28,13 +29,20 @@ CORNERS = ("all_stance", "all_swing", "one_foot", "switch_on_tick_20", "attitude
 
 
 # ------------------------------------------------------------------------------------------------ input sequences (no GPU)
-def trot_tables(synth_mod, B, k):
-    """Gait matrices (B, N_GAIT, 4) of tick k: a 16-row trot period that advances one row every 10 ticks (k_mpc), robot b two
-    rows ahead of robot b - 1; rows 16.. are zero rows, as in the planners' matrices."""
-    g = np.zeros((B, N_GAIT, 4))
+def trot_tables(synth_mod, B, k, n_gait=N_GAIT, k_mpc=10, full=(), still=()):
+    """Gait matrices (B, n_gait, 4) of tick k: a 16-row trot period that advances one row every k_mpc ticks, robot b two
+    rows ahead of robot b - 1; rows 16.. are zero rows, as in the planners' matrices.  The robots of `full` have the period
+    repeated through all n_gait rows (no zero row); those of `still` n_gait rows equal to their row 0 -- one stance pair for
+    good, so that the scan for the first row that differs from row 0 ends at n_gait."""
+    g = np.zeros((B, n_gait, 4))
     period = synth_mod.gait_pattern("trot", 16)
     for b in range(B):
-        g[b, :16] = np.roll(period, -(k // 10 + 2 * b), axis=0)
+        rolled = np.roll(period, -(k // k_mpc + 2 * b), axis=0)
+        g[b, :16] = rolled
+        if b in full:
+            g[b] = rolled[np.arange(n_gait) % 16]
+        if b in still:
+            g[b] = period[(2 * b) % 16]
     return g
 
 
@@ -54,19 +62,32 @@ def _yaw_quat(a):
     return np.array([0.0, 0.0, np.sin(a / 2), np.cos(a / 2)])
 
 
-def trot_sequence(synth_mod, B, ticks, seed):
-    sen = synth_mod.SyntheticSensors(B, seed)
+def trot_sequence(synth_mod, B, ticks, seed, dt=DT, **tables):
+    sen = synth_mod.SyntheticSensors(B, seed, dt)
     goals = np.random.default_rng(seed).uniform(-0.2, 0.2, (B, 3, 4))
-    return [dict(sensors=sen.step(k), gait=trot_tables(synth_mod, B, k), goals=goals) for k in range(ticks)]
+    return [dict(sensors=sen.step(k), gait=trot_tables(synth_mod, B, k, **tables), goals=goals) for k in range(ticks)]
 
 
-def planner_sequence(oracle_mod, synth_mod, B=5, ticks=60, seed=8):
+# the other configuration (tests/test_gpu_controller.py's ALT_CFG): the tick halved, gait matrices of 26 rows
+ALT_DT, ALT_N_GAIT, ALT_K_MPC = 0.001, 26, 20
+ALT_HANDLE = dict(n_steps=12, N_gait=ALT_N_GAIT, dt_mpc=0.02, T_gait=0.40, dt_wbc=ALT_DT)
+ALT_PLANNER = dict(dt_mpc=0.02, dt_wbc=ALT_DT, T_gait=0.40, T_mpc=0.24, N_gait=ALT_N_GAIT, k_mpc=ALT_K_MPC, h_ref=0.21)
+ALT_OPTIONS = dict(dt=ALT_DT, handle=ALT_HANDLE, planner_init=dict(k_mpc=ALT_K_MPC, h_ref=0.21))  # (sequences()' options)
+ALT_FULL, ALT_STILL = (2, 9), (5, 16)  # robots whose 26 rows hold no zero row / are all their row 0 (block 1's only quad among them)
+
+
+def alt_trot_sequence(synth_mod, B=17, ticks=120, seed=17):
+    return trot_sequence(synth_mod, B, ticks, seed, ALT_DT, n_gait=ALT_N_GAIT, k_mpc=ALT_K_MPC, full=ALT_FULL, still=ALT_STILL)
+
+
+def planner_sequence(oracle_mod, synth_mod, B=5, ticks=60, seed=8, **planner):
     """Gait and foot positions of oracle planners stepped after the estimator on every tick (scripts/Controller.py:213-236), gait
-    codes changing on tick 35: what the handle's own planner holds when it is given the same q7 / vref / code."""
-    plan = [oracle_mod.Planner() for _ in range(B)]
-    sen = synth_mod.SyntheticSensors(B, seed)
+    codes changing on tick 35: what the handle's own planner holds when it is given the same q7 / vref / code.  planner: the
+    oracle planners' configuration where it is not the default one."""
+    plan = [oracle_mod.Planner(**planner) for _ in range(B)]
+    sen = synth_mod.SyntheticSensors(B, seed, planner.get("dt_wbc", DT))
     vref = np.random.default_rng(seed).uniform(-0.4, 0.4, (B, 6)) * np.array([1.5, 0.8, 0, 0, 0, 1.0])
-    q7 = np.tile(np.array([0.0, 0.0, 0.2229, 0.0, 0.0, 0.0, 1.0]), (B, 1))
+    q7 = np.tile(np.array([0.0, 0.0, planner.get("h_ref", 0.2229), 0.0, 0.0, 0.0, 1.0]), (B, 1))
     seq = []
     for k in range(ticks):
         code = np.array([[1, 2, 3, 4, 5][b % 5] if k == 35 else 0 for b in range(B)], np.int32)
@@ -110,6 +131,8 @@ def sequences(oracle_mod, synth_mod):
         perfect, seq = corner_sequence(corner)
         yield corner, 4, dict(perfect=perfect), seq
     yield "tuned", 4, dict(kalman=TUNED), trot_sequence(synth_mod, 4, 40, 11)
+    yield "alt_trot_b17", 17, ALT_OPTIONS, alt_trot_sequence(synth_mod)
+    yield "alt_planner", 5, ALT_OPTIONS, planner_sequence(oracle_mod, synth_mod, seed=18, **ALT_PLANNER)
 
 
 def kalman_err(got, ref):
@@ -160,10 +183,11 @@ def _device_step(eng, tick, planner=False, out=None):
     return {k: v.cpu().numpy() for k, v in o.items()}
 
 
-def _compare(eng, out, refs, k, worst):
+def _compare(eng, out, refs, k, worst, robots=None):
+    """robots: the instances of the handle the checker objects stand for (None: 0, 1, ...)."""
     import qrw_hip
 
-    for b, r in enumerate(refs):
+    for b, r in enumerate(refs) if robots is None else zip(robots, refs):
         where = (k, b)
         figures = dict(q_filt=kalman_err(out["q_filt"][b], r.q_filt), v_filt=kalman_err(out["v_filt"][b], r.v_filt),
                        X=kalman_err(eng.estimator_kalman_get("X", b), r.X), P=covariance_err(eng.estimator_kalman_get("P", b), r.P))
@@ -188,12 +212,12 @@ def _run_against_checker(ekn, B, options, seq, planner=False):
 
     import qrw_hip
 
-    eng = qrw_hip.Batch(B, 16, N_GAIT)
+    eng = qrw_hip.Batch(B, **options.get("handle", dict(n_steps=16, N_gait=N_GAIT)))
     if planner:
-        eng.planner_init()
+        eng.planner_init(**options.get("planner_init", {}))
     kalman = options.get("kalman", True)
     eng.estimator_init(H_INIT, options.get("perfect", False), kalman=kalman)
-    refs = [ekn.Estimator(DT, H_INIT, options.get("perfect", False), kalman=kalman) for _ in range(B)]
+    refs = [ekn.Estimator(options.get("dt", DT), H_INIT, options.get("perfect", False), kalman=kalman) for _ in range(B)]
     worst, pout = {}, None
     for k, tick in enumerate(seq):
         out = _device_step(eng, tick, planner)
@@ -242,6 +266,29 @@ def test_hand_made_rows(oracle_mod, ekn, corner):
         assert rpy[0, 2] > 3.14 and rpy[1, 2] < -3.14 and rpy[2, 1] == np.pi / 2 and rpy[3, 1] == -np.pi / 2
 
 
+def test_other_time_step_and_gait_table_length(oracle_mod, synth_mod, ekn):
+    """dt_wbc = 0.001 and gait matrices of 26 rows (ALT_HANDLE), B = 17, 120 ticks, noisy sensors: Q = sigma^2 dt^2, the
+    prediction and the two first-order filters' coefficients all take the handle's dt.  Robots 2 and 9 have no zero row in their
+    26, robots 5 and 16 have 26 equal rows (the scan for the end of the phase ends at N_gait); the tables advance six rows, so
+    that about half of the others switch their stance pair.  And the time step matters: the checker at 0.002 gives another X."""
+    seq = alt_trot_sequence(synth_mod)
+    assert all(t["gait"].shape == (17, ALT_N_GAIT, 4) for t in seq)
+    assert all(seq[0]["gait"][b].any(axis=1).all() for b in ALT_FULL + ALT_STILL) and not seq[0]["gait"][0, 16:].any()
+    assert all((seq[-1]["gait"][b] == seq[-1]["gait"][b, 0]).all() for b in ALT_STILL)
+    eng, refs = _run_against_checker(ekn, 17, ALT_OPTIONS, seq)
+    assert all(r.k_log == 120 for r in refs) and {r.remaining_steps for r in refs} >= {ALT_N_GAIT, 1, 7}
+    plain = ekn.Estimator(DT, H_INIT)
+    for tick in seq:
+        checker_step(plain, tick, 0)
+    assert kalman_err(plain.X, refs[0].X) > 1e3 * KALMAN_BOUND
+
+
+def test_other_configuration_on_the_handles_planner_state(oracle_mod, synth_mod, ekn):
+    """The same configuration with d_gait / d_goals NULL: the handle's planner (k_mpc = 20, T_gait = 0.40, 26-row matrices as
+    64-bit column masks) against oracle planners of that configuration, B = 5, 60 ticks."""
+    _run_against_checker(ekn, 5, ALT_OPTIONS, planner_sequence(oracle_mod, synth_mod, seed=18, **ALT_PLANNER), planner=True)
+
+
 def test_non_default_tuning(oracle_mod, synth_mod, ekn):
     """All five tuning values changed, in the kernel and in the checker; and they matter: the default tuning gives another X."""
     seq = trot_sequence(synth_mod, 4, 40, 11)
@@ -274,6 +321,45 @@ def _identical(rec_a, rec_b, robots=slice(None)):
         assert len(a) == len(b)
         for i, (x, y) in enumerate(zip(a, b)):
             assert np.array_equal(x[robots], y[robots], equal_nan=True), (k, i)
+
+
+B83 = 83  # six blocks of 16 quads (the last holding three) for the step kernels, two blocks of 64 robots for estimator_init_kernel
+
+
+def block_coverage(synth_mod, kalman, make_ref, compare):
+    """estimator_init and 20 ticks at B = 83, robot i fed the inputs of robot src[i] of the 17-robot trot sequence (a fixed
+    permutation, so that equal robots do not sit 17 apart): every output and item of robot i is bit for bit that of robot src[i]
+    in a B = 17 handle on every tick, and the first tick of robots 64..82 -- initialised by the init kernel's second block --
+    is compared with the checker (make_ref() -> a fresh checker object; compare(eng, out, refs, robots))."""
+    import qrw_hip
+
+    seq = trot_sequence(synth_mod, 17, 20, 19)
+    src = np.random.default_rng(83).permutation(B83) % 17
+    assert set(src) == set(range(17))
+    wide = [dict(sensors={n: v[src] for n, v in t["sensors"].items()}, gait=t["gait"][src], goals=t["goals"][src]) for t in seq]
+    small, large = qrw_hip.Batch(17, 16, N_GAIT), qrw_hip.Batch(B83, 16, N_GAIT)
+    for eng in (small, large):
+        eng.estimator_init(H_INIT, kalman=kalman)
+    rec = _record(large, wide[:1], B83)
+    second_block = list(range(64, B83))
+    refs = [make_ref() for _ in second_block]
+    for b, r in zip(second_block, refs):
+        checker_step(r, wide[0], b)
+    compare(large, dict(zip(("q_filt", "v_filt", "rpy", "v_secu"), rec[0][:4])), refs, second_block)
+    rec += _record(large, wide[1:], B83)
+    want = _record(small, seq, 17)
+    assert len(rec) == len(want) == 20
+    for k, (a, b) in enumerate(zip(rec, want)):
+        assert len(a) == len(b)
+        for i, (x, y) in enumerate(zip(a, b)):
+            assert np.array_equal(x, y[src], equal_nan=True), (k, i, np.nonzero(np.any((x != y[src]).reshape(B83, -1), axis=1))[0])
+    assert all(np.isfinite(x).all() for x in rec[-1])
+
+
+def test_block_coverage(oracle_mod, synth_mod, ekn):
+    """block_coverage for the Kalman filter: X, P and Z among the items."""
+    block_coverage(synth_mod, True, lambda: ekn.Estimator(DT, H_INIT),
+                   lambda eng, out, refs, robots: _compare(eng, out, refs, 0, {}, robots))
 
 
 def test_reinitialisation_in_either_direction_is_a_fresh_handle(synth_mod):

@@ -77,16 +77,18 @@ def _fd_states(sn, n=B17, seed=11):
     return states
 
 
-def fd_spread(sn, states):
-    """The checker against itself: float64 against longdouble solve, and every input moved up by one ulp; relative to max(1, |a|_inf)."""
+def fd_spread(sn, states, prm=None):
+    """The checker against itself: float64 against longdouble solve, and every input moved up by one ulp; relative to max(1, |a|_inf).
+    prm: the contact parameters (None: the defaults)."""
     solve, ulp = 0.0, 0.0
+    prm = sn.DEFAULTS if prm is None else dict(sn.DEFAULTS, **prm)
     for q, v, tau, fe, _ in states:
         for f_ext in (None, fe):
-            a, _, _ = sn.forward_dynamics(q, v, tau, f_ext=f_ext)
-            al, _, _ = sn.forward_dynamics(q, v, tau, f_ext=f_ext, solve=sn.solve_longdouble)
+            a, _, _ = sn.forward_dynamics(q, v, tau, prm, f_ext=f_ext)
+            al, _, _ = sn.forward_dynamics(q, v, tau, prm, f_ext=f_ext, solve=sn.solve_longdouble)
             qp = np.nextafter(q, np.inf)
             qp[3:7] = q[3:7]  # (the quaternion stays a unit one)
-            ap, _, _ = sn.forward_dynamics(qp, np.nextafter(v, np.inf), np.nextafter(tau, np.inf), f_ext=f_ext)
+            ap, _, _ = sn.forward_dynamics(qp, np.nextafter(v, np.inf), np.nextafter(tau, np.inf), prm, f_ext=f_ext)
             scale = max(1.0, np.abs(a).max())
             solve = max(solve, float(np.abs(a - np.asarray(al, dtype=float)).max()) / scale)
             ulp = max(ulp, np.abs(a - ap).max() / scale)
@@ -153,14 +155,14 @@ def _tick_case(sn, B=B17, seed=3):
     return q0, command
 
 
-def tick_spread(sn, B=B17, ticks=60):
+def tick_spread(sn, B=B17, ticks=60, **params):
     """The checker against itself over its own free run of the teacher-forced case: every tick once more from the state moved up by
     one ulp (the quaternion kept); largest difference of a state item or output relative to max(1, |item|_inf).  Also the
-    smallest |d| of the run and the numbers of feet in contact it saw."""
+    smallest |d| of the run and the numbers of feet in contact it saw.  params: simulator parameters other than the defaults."""
     q0, command = _tick_case(sn, B)
     spread, smallest, seen = 0.0, np.inf, set()
     for b in range(B):
-        r, p = sn.SimNumpy(q0[b]), sn.SimNumpy(q0[b])
+        r, p = sn.SimNumpy(q0[b], **params), sn.SimNumpy(q0[b], **params)
         for k in range(ticks):
             c = [x if x is None else x[b] for x in command(k)]
             qp = np.nextafter(r.q, np.inf)
@@ -175,18 +177,18 @@ def tick_spread(sn, B=B17, ticks=60):
     return spread, smallest, seen
 
 
-def _compare_tick(got_state, got_out, refs, k):
+def _compare_tick(got_state, got_out, refs, k, bound=TICK_BOUND):
     worst = 0.0
     for b, r in enumerate(refs):
         assert r.status == 0 and got_state["status"][b] == 0 and got_state["tick"][b] == r.tick, (k, b)
         for name, ref in (("q", r.q), ("v", r.v), ("prev_o_imuVel", r.prev)):
             e = _rel(got_state[name][b], ref)
             worst = max(worst, e)
-            assert e <= TICK_BOUND, (name, k, b, e)
+            assert e <= bound, (name, k, b, e)
         for name in OUT_KEYS:
             e = _rel(got_out[name][b], r.out[name])
             worst = max(worst, e)
-            assert e <= TICK_BOUND, (name, k, b, e)
+            assert e <= bound, (name, k, b, e)
     return worst
 
 

@@ -57,11 +57,12 @@ def set_terrain(eng, T, origin=None):
     eng.sim_set_terrain(T.H, T.dx, T.dy, x0=T.x0, y0=T.y0, origin=origin)
 
 
-def _settle(stn, q, T, origin, delta, deepest=True):
-    """q with the base height set so that the deepest foot (or, deepest=False, the shallowest one) has d = delta."""
+def _settle(stn, q, T, origin, delta, deepest=True, prm=None):
+    """q with the base height set so that the deepest foot (or, deepest=False, the shallowest one) has d = delta under the
+    parameters prm (None: the defaults; only foot_radius enters)."""
     q = q.copy()
     q[2] = 0.0
-    _, d0, _ = stn.contact_forces(q, np.zeros(18), stn.DEFAULTS, T, origin)
+    _, d0, _ = stn.contact_forces(q, np.zeros(18), stn.DEFAULTS if prm is None else prm, T, origin)
     nz = []
     for j in range(4):  # d is linear in the base height: d = d0 - n_z z
         pf = q[:3] + stn.sn.quat_to_rot(q[3:7]) @ stn.oracle.fixed_feet(q[7:], np.zeros(12))[0][j]
@@ -72,8 +73,9 @@ def _settle(stn, q, T, origin, delta, deepest=True):
     return q
 
 
-def _fd_states(stn, which, n=B17, seed=13):
-    """(q19, v18, tau12, f_ext, origin (2,), wanted contacts or None, outside the field) x n on field `which`."""
+def _fd_states(stn, which, n=B17, seed=13, prm=None):
+    """(q19, v18, tau12, f_ext, origin (2,), wanted contacts or None, outside the field) x n on field `which`, settled under the
+    parameters prm (None: the defaults)."""
     rng = np.random.default_rng(seed + (0 if which == "rough" else 100))
     T, Q = FIELDS[which](stn), stn.Q_STANCE
     xmax, ymax = T.x0 + T.dx * (T.H.shape[1] - 1), T.y0 + T.dy * (T.H.shape[0] - 1)
@@ -119,7 +121,7 @@ def _fd_states(stn, which, n=B17, seed=13):
     states = []
     for q, v, origin, delta, deepest, want, outside in corners[:n]:
         origin = np.array(origin, dtype=float)
-        q = _settle(stn, q, T, origin, delta, deepest)
+        q = _settle(stn, q, T, origin, delta, deepest, prm)
         states.append((q, np.array(v, dtype=float), rng.normal(size=12), rng.normal(size=6) * [3.0, 3.0, 3.0, 0.3, 0.3, 0.3], origin, want, outside))
     assert len(states) == n
     return T, states
@@ -149,27 +151,30 @@ def check_identical_robots(stn, T, states):
     assert len({tuple(c[:2] for c in cs) for cs in cells}) == 3, cells
 
 
-def fd_spread(stn):
-    """The checker against itself on the forward-dynamics states of both fields: float64 against longdouble solve, and every input
-    moved up by one ulp (the quaternion kept); relative to max(1, |a|_inf)."""
+def fd_spread(stn, fields=tuple(FIELDS), prm=None):
+    """The checker against itself on the forward-dynamics states of the fields (both by default): float64 against longdouble solve,
+    and every input moved up by one ulp (the quaternion kept); relative to max(1, |a|_inf).  prm: parameters other than the
+    defaults, under which the states are settled too."""
     solve, ulp = 0.0, 0.0
-    for which in FIELDS:
-        T, states = _fd_states(stn, which)
+    prm = stn.DEFAULTS if prm is None else dict(stn.DEFAULTS, **prm)
+    for which in fields:
+        T, states = _fd_states(stn, which, prm=prm)
         for q, v, tau, fe, origin, _, _ in states:
             for f_ext in (None, fe):
-                a, _, _ = stn.forward_dynamics(q, v, tau, T, origin, f_ext=f_ext)
-                al, _, _ = stn.forward_dynamics(q, v, tau, T, origin, f_ext=f_ext, solve=stn.sn.solve_longdouble)
+                a, _, _ = stn.forward_dynamics(q, v, tau, T, origin, prm, f_ext=f_ext)
+                al, _, _ = stn.forward_dynamics(q, v, tau, T, origin, prm, f_ext=f_ext, solve=stn.sn.solve_longdouble)
                 qp = np.nextafter(q, np.inf)
                 qp[3:7] = q[3:7]
-                ap, _, _ = stn.forward_dynamics(qp, np.nextafter(v, np.inf), np.nextafter(tau, np.inf), T, origin, f_ext=f_ext)
+                ap, _, _ = stn.forward_dynamics(qp, np.nextafter(v, np.inf), np.nextafter(tau, np.inf), T, origin, prm, f_ext=f_ext)
                 scale = max(1.0, np.abs(a).max())
                 solve = max(solve, float(np.abs(a - np.asarray(al, dtype=float)).max()) / scale)
                 ulp = max(ulp, np.abs(a - ap).max() / scale)
     return solve, ulp
 
 
-def _tick_case(stn, B=B17, seed=7):
-    """Robots dropped onto / pressed into the rough field under PD commands that change every tick (test_gpu_sim's law)."""
+def _tick_case(stn, B=B17, seed=7, prm=None):
+    """Robots dropped onto / pressed into the rough field under PD commands that change every tick (test_gpu_sim's law); the
+    initial heights settled under the parameters prm (None: the defaults)."""
     rng = np.random.default_rng(seed)
     T = rough_field(stn)
     origin = rng.uniform(-0.004, 0.004, (B, 2))
@@ -178,7 +183,7 @@ def _tick_case(stn, B=B17, seed=7):
     q0[:, 3:7] = [_rpy_quat(*(0.03 * rng.normal(size=2)), 0.03 * rng.normal()) for _ in range(B)]
     q0[:, 7:] = stn.Q_STANCE + 0.02 * rng.normal(size=(B, 12))
     for b, delta in enumerate(rng.uniform(-0.02, 0.015, B)):  # from the lowest foot 2 cm above the ground to 1.5 cm into it
-        q0[b] = _settle(stn, q0[b], T, origin[b], delta)
+        q0[b] = _settle(stn, q0[b], T, origin[b], delta, prm=prm)
     phase, amp = rng.uniform(0, 2 * np.pi, (B, 12)), rng.uniform(0.0, 0.25, (B, 1))
 
     def command(k):
@@ -193,14 +198,15 @@ def _tick_case(stn, B=B17, seed=7):
     return T, origin, q0, command
 
 
-def tick_spread(stn, B=B17, ticks=60):
+def tick_spread(stn, B=B17, ticks=60, seed=7, **params):
     """The checker against itself over its own free run of the teacher-forced case: every tick once more from the state moved up by
     one ulp (the quaternion kept).  Returns the spread, the smallest |d|, |fu - fv| and edge distance of the run (both copies),
-    the numbers of feet in contact and the triangle kinds it saw."""
-    T, origin, q0, command = _tick_case(stn, B)
+    the numbers of feet in contact and the triangle kinds it saw.  params: simulator parameters other than the defaults (the
+    initial heights are settled under them)."""
+    T, origin, q0, command = _tick_case(stn, B, seed, prm=dict(stn.DEFAULTS, **params) if params else None)
     spread, d_min, diag_min, edge_min, seen, kinds = 0.0, np.inf, np.inf, np.inf, set(), set()
     for b in range(B):
-        r, p = stn.SimTerrainNumpy(q0[b], T, origin[b]), stn.SimTerrainNumpy(q0[b], T, origin[b])
+        r, p = stn.SimTerrainNumpy(q0[b], T, origin[b], **params), stn.SimTerrainNumpy(q0[b], T, origin[b], **params)
         for k in range(ticks):
             c = [x if x is None else x[b] for x in command(k)]
             qp = np.nextafter(r.q, np.inf)
@@ -218,14 +224,16 @@ def tick_spread(stn, B=B17, ticks=60):
 
 
 # ------------------------------------------------------------------------------------------------ forward dynamics
-def _compare_fd(oracle_mod, stn, eng, T, states, with_f_ext, bound=FD_BOUND):
+def _compare_fd(oracle_mod, stn, eng, T, states, with_f_ext, bound=FD_BOUND, **params):
+    """params: simulator parameters other than the defaults, given to the device and to the checker alike."""
     fe = np.stack([s[3] for s in states]) if with_f_ext else None
+    prm = dict(stn.DEFAULTS, **params)
     a_dev, f_dev = eng.test_sim_forward_dynamics(np.stack([s[0] for s in states]), np.stack([s[1] for s in states]),
-                                                 np.stack([s[2] for s in states]), f_ext=fe)
+                                                 np.stack([s[2] for s in states]), f_ext=fe, **params)
     worst, contacts, kinds = 0.0, [], set()
     for i, (q, v, tau, fx, origin, want, outside) in enumerate(states):
         f_ext, cells = (fx if with_f_ext else None), []
-        a, f, d = stn.forward_dynamics(q, v, tau, T, origin, f_ext=f_ext, cells=cells)
+        a, f, d = stn.forward_dynamics(q, v, tau, T, origin, prm, f_ext=f_ext, cells=cells)
         kinds |= check_switches(d, cells, outside)
         if outside:
             assert any(fu in (0.0, 1.0) or fv in (0.0, 1.0) for _, _, fu, fv in cells), (i, cells)
