@@ -201,8 +201,20 @@ typedef struct {
 
 /* Replaces Gait::initialize (src/Gait.cpp:19-36), StatePlanner::initialize (src/StatePlanner.cpp:12-19),
  * FootstepPlanner::initialize (src/FootstepPlanner.cpp:22-49), FootTrajectoryGenerator::initialize
- * (src/FootTrajectoryGenerator.cpp:22-38). Returns -3 where Gait::initialize throws (N_gait too small). */
+ * (src/FootTrajectoryGenerator.cpp:22-38). Returns -3 where Gait::initialize throws (N_gait too small).
+ *
+ * The size rule. The gait matrices are 64-bit column masks (bit i = row i), so N_gait <= 63 (-1 otherwise), and -3 is returned,
+ * before anything is launched, unless
+ *     n_steps + 1 <= N_gait   and   rows_needed(T_gait, dt_mpc) <= N_gait,
+ *     rows_needed = max(2 lround(0.5 T_gait / dt_mpc), 4 lround(0.25 T_gait / dt_mpc), lround(T_gait / dt_mpc)):
+ * the rows the pacing / bounding / trot generators, the walk generator and the static generator write. Gait::initialize tests
+ * the last of the three only (src/Gait.cpp:30-31) and a joystick code then writes outside the matrices when another is larger.
+ * A period that fills the table exactly (rows_needed == N_gait) is legal and means "row N_gait counts as a zero row"; the
+ * reference reads past its matrices there. A refused handle stays uninitialised: its planner calls return -1.
+ * qrw_gait_table_fits asks that rule (with N_gait <= 63) of a handle's configuration without initialising or launching
+ * anything: 1 fits, 0 qrw_planner_init would refuse, -1 null handle. */
 int qrw_planner_init(qrw_handle h, const qrw_planner_config *pc, void *stream);
+int qrw_gait_table_fits(qrw_handle h);
 
 /* One control iteration of the planners, in the order of scripts/Controller.py:222-236:
  * Gait::updateGait(k, k_mpc, q, code) (src/Gait.cpp:184-192), FootstepPlanner::updateFootsteps(k % k_mpc == 0 && k != 0,

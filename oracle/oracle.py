@@ -8,6 +8,7 @@ The classes mirror the reference binding surface (python/gepadd.cpp:22-31,186-19
 so that parity tests read like calls into the reference.
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -96,6 +97,8 @@ def load(fast=False):
         "planner_oracle_create": (vp, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, _dp,
                                        C.c_double, C.c_double, _dp, _dp]),
         "planner_oracle_destroy": (None, [vp]),
+        "planner_oracle_rows_needed": (C.c_int, [C.c_double, C.c_double]),
+        "planner_oracle_table_fits": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double]),
         "planner_oracle_gait_update": (None, [vp, C.c_int, _dp, C.c_int]),
         "planner_oracle_footsteps_update": (None, [vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
         "planner_oracle_traj_update": (None, [vp, C.c_int, _dp]),
@@ -108,6 +111,7 @@ def load(fast=False):
         "planner_oracle_get_footsteps": (None, [vp, _dp, _dp, _dp]),
         "planner_oracle_get_feet": (None, [vp, _dp, _dp, _dp, _dp, _dp]),
         "planner_oracle_get_Rz": (None, [vp, _dp]),
+        "planner_oracle_get_ft_target": (None, [vp, _dp]),
         "mpc_oracle_run_batch": (C.c_int, [C.POINTER(vp), C.c_int, _ip, _dp, _dp, _dp, C.c_int]),
         "wbc_oracle_compute_batch": (C.c_int, [C.POINTER(vp), C.c_int] + [_dp] * 11 + [C.c_int]),
     }
@@ -528,7 +532,7 @@ class Planner:
         sh = _arr(shoulders, (3, 4))
         it = _arr(init_target if init_target is not None else sh, (3, 4))
         ip = _arr(init_foot_pos if init_foot_pos is not None else sh, (3, 4))
-        self.N_gait, self.n_steps = int(N_gait), int(round(T_mpc / dt_mpc))
+        self.N_gait, self.n_steps = int(N_gait), int(math.floor(T_mpc / dt_mpc + 0.5))  # (lround, as planner_oracle_create)
         self._h = self._lib.planner_oracle_create(dt_mpc, dt_wbc, T_gait, T_mpc, int(N_gait), int(k_mpc), h_ref,
                                                   _ptr(sh), max_height, lock_time, _ptr(it), _ptr(ip))
         if not self._h:
@@ -582,6 +586,12 @@ class Planner:
         r = np.zeros((3, 3))
         self._lib.planner_oracle_get_Rz(self._h, _ptr(r))
         return r
+
+    def ft_target(self):
+        """FootTrajectoryGenerator's targetFootstep_ (what item 17 of qrw_planner_get_host holds)."""
+        t = np.zeros((3, 4))
+        self._lib.planner_oracle_get_ft_target(self._h, _ptr(t))
+        return t
 
     def footsteps(self):
         f, t, ot = np.zeros((self.N_gait, 12)), np.zeros((3, 4)), np.zeros((3, 4))

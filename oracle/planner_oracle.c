@@ -7,7 +7,8 @@
  *   FootstepPlanner          src/FootstepPlanner.cpp:22-249
  *   FootTrajectoryGenerator  src/FootTrajectoryGenerator.cpp:22-151
  * in the order scripts/Controller.py:222-236 calls them.  pinocchio::rpy::matrixToRpy (third-party,
- * absent) is restated from its published definition.  PARITY UNPINNED (no reference vectors).
+ * absent) is restated from its published definition.  PARITY UNPINNED (no reference vectors); a second implementation written
+ * independently from the same four files, tests/planner_numpy.py, is held against this one (tests/test_planner_second_impl.py).
  */
 #include <math.h>
 #include <stdlib.h>
@@ -384,6 +385,20 @@ void planner_oracle_traj_update(planner_oracle *o, int k, const double *target3x
   }
 }
 
+/* The size rule: the rows the gait generators write (create_* above) must fit the table. */
+int planner_oracle_rows_needed(double T_gait, double dt_mpc) {
+  double per = T_gait / dt_mpc;
+  if (!(per >= 0.0 && per < 1.0e6)) return 2147483647;
+  long half = 2 * lround(0.5 * T_gait / dt_mpc), quarter = 4 * lround(0.25 * T_gait / dt_mpc), whole = lround(T_gait / dt_mpc);
+  long m = half;
+  if (quarter > m) m = quarter;
+  if (whole > m) m = whole;
+  return (int)m;
+}
+int planner_oracle_table_fits(int N_gait, int n_steps, double T_gait, double dt_mpc) {
+  return N_gait >= 1 && N_gait <= 63 && n_steps >= 1 && n_steps + 1 <= N_gait && planner_oracle_rows_needed(T_gait, dt_mpc) <= N_gait;
+}
+
 /* constructors + initialize() of the four classes (Gait.cpp:19-36, StatePlanner.cpp:12-19, FootstepPlanner.cpp:22-49,
  * FootTrajectoryGenerator.cpp:22-38), with the arguments scripts/Controller.py:119-137 passes */
 planner_oracle *planner_oracle_create(double dt_mpc, double dt_wbc, double T_gait, double T_mpc, int N_gait, int k_mpc,
@@ -392,10 +407,14 @@ planner_oracle *planner_oracle_create(double dt_mpc, double dt_wbc, double T_gai
   planner_oracle *o = (planner_oracle *)calloc(1, sizeof(*o));
   o->dt = dt_mpc; o->T_gait = T_gait; o->T_mpc = T_mpc; o->N_gait = N_gait; o->k_mpc = k_mpc;
   o->n_steps = (int)lround(T_mpc / dt_mpc);
-  if ((o->n_steps > N_gait) || ((int)lround(T_gait / dt_mpc) > N_gait)) { free(o); return NULL; } /* Gait.cpp:30-31 throws */
-  o->past = (double *)calloc(N_gait * 4, sizeof(double));
-  o->cur = (double *)calloc(N_gait * 4, sizeof(double));
-  o->des = (double *)calloc(N_gait * 4, sizeof(double));
+  /* Gait.cpp:30-31 throws when lround(T_gait / dt) > N_gait; the generators above write up to planner_oracle_rows_needed rows,
+   * and the device keeps its matrices in 64-bit masks and rolls n_steps + 1 rows of the past gait: one rule for both sides */
+  if (!planner_oracle_table_fits(N_gait, o->n_steps, T_gait, dt_mpc)) { free(o); return NULL; }
+  /* one row more than N_gait, always zero: Gait.cpp reads row N_gait (create_gait_f :116, rollGait :236-248, getPhaseDuration
+   * :147-160) when a period fills the table, which is outside its matrices; here that row exists and is a zero row */
+  o->past = (double *)calloc((N_gait + 1) * 4, sizeof(double));
+  o->cur = (double *)calloc((N_gait + 1) * 4, sizeof(double));
+  o->des = (double *)calloc((N_gait + 1) * 4, sizeof(double));
   create_trot(o);
   create_gait_f(o);
   o->h_ref = h_ref;
@@ -449,6 +468,9 @@ void planner_oracle_get_footsteps(const planner_oracle *o, double *fsteps_Ngx12,
   if (o_target3x4) memcpy(o_target3x4, o->o_targetFootstep, sizeof(o->o_targetFootstep));
 }
 void planner_oracle_get_Rz(const planner_oracle *o, double *out9) { memcpy(out9, o->Rz, sizeof(o->Rz)); } /* FootstepPlanner::getRz :236 */
+/* FootTrajectoryGenerator's targetFootstep_ (3x4): initialize's targetFootstepIn, then rows 0 / 1 of a swinging foot while its
+ * coefficients are being updated (FootTrajectoryGenerator.cpp:33,93-94) */
+void planner_oracle_get_ft_target(const planner_oracle *o, double *out3x4) { memcpy(out3x4, o->ft_target, sizeof(o->ft_target)); }
 void planner_oracle_get_feet(const planner_oracle *o, double *pos, double *vel, double *acc, double *t0s, double *t_swing) {
   if (pos) memcpy(pos, o->position, sizeof(o->position));
   if (vel) memcpy(vel, o->velocity, sizeof(o->velocity));

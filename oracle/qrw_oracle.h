@@ -113,6 +113,10 @@ planner_oracle *planner_oracle_create(double dt_mpc, double dt_wbc, double T_gai
                                       double h_ref, const double *shoulders3x4, double max_height, double lock_time,
                                       const double *init_target3x4, const double *init_foot_pos3x4);
 void planner_oracle_destroy(planner_oracle *o);
+/* the size rule planner_oracle_create applies (NULL where it refuses): the largest number of rows a gait generator writes, and
+ * N_gait <= 63 && n_steps + 1 <= N_gait && rows_needed <= N_gait */
+int planner_oracle_rows_needed(double T_gait, double dt_mpc);
+int planner_oracle_table_fits(int N_gait, int n_steps, double T_gait, double dt_mpc);
 void planner_oracle_gait_update(planner_oracle *o, int k, const double *q7, int code);          /* Gait::updateGait */
 void planner_oracle_footsteps_update(planner_oracle *o, int refresh, int k, const double *q7, const double *b_v,
                                      const double *b_vref, double *out_target3x4);              /* FootstepPlanner::updateFootsteps */
@@ -126,6 +130,7 @@ void planner_oracle_get_flags(const planner_oracle *o, double *out4); /* newPhas
 void planner_oracle_get_xref(const planner_oracle *o, double *xref);
 void planner_oracle_get_footsteps(const planner_oracle *o, double *fsteps_Ngx12, double *target3x4, double *o_target3x4);
 void planner_oracle_get_Rz(const planner_oracle *o, double *out3x3); /* FootstepPlanner::getRz, FootstepPlanner.cpp:236 */
+void planner_oracle_get_ft_target(const planner_oracle *o, double *out3x4); /* FootTrajectoryGenerator targetFootstep_ */
 void planner_oracle_get_feet(const planner_oracle *o, double *pos, double *vel, double *acc, double *t0s, double *t_swing);
 
 /* batched helpers for the bench's cpu_baseline leg: `threads` OpenMP threads over instances */

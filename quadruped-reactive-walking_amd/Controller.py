@@ -126,7 +126,7 @@ class Controller_batch:
         self.B = int(batch)
         self.dev = torch.device("cuda:%d" % device)
         self.k, self.k_mpc, self.h_ref, self.dt_wbc = 0, int(k_mpc), float(h_ref), float(dt_wbc)
-        self.n_steps = int(round(T_mpc / dt_mpc))
+        self.n_steps = qrw_hip.lround(float(T_mpc) / float(dt_mpc))
         self._b = qrw_hip.Batch(self.B, n_steps=self.n_steps, N_gait=int(N_gait), dt_mpc=float(dt_mpc),
                                 T_gait=float(T_gait), dt_wbc=float(dt_wbc), device=device)
         qi = np.broadcast_to(np.asarray(q_init, dtype=np.float64).reshape(-1, 12), (self.B, 12))
@@ -515,7 +515,7 @@ class Controller_groups(Controller_batch):
         self.B, self.G, self.Bs = int(batch), G, int(batch) // G
         self.dev = torch.device("cuda:%d" % device)
         self.k, self.k_mpc, self.h_ref, self.dt_wbc = 0, int(k_mpc), float(h_ref), float(dt_wbc)
-        self.n_steps = int(round(T_mpc / dt_mpc))
+        self.n_steps = qrw_hip.lround(float(T_mpc) / float(dt_mpc))
         self.multiprocessing, self.fused = bool(multiprocessing), bool(fused)
         self._fleet_result = torch.zeros((self.B, 5, 12), dtype=torch.float64, device=self.dev)
         # stagger: group g starts g * k_mpc / G fleet ticks late, so that the groups solve on different ticks (the reference solves

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "controller_glue.h"
+#include "gait_masks.h"
 #include "qrw_device.h"
 #include "qrw_kernels.h"
 
@@ -75,49 +76,9 @@ __host__ __device__ inline Lay make_layout(int Ng) {
   return L;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// The reference keeps the three gait matrices (past / current / desired, N_gait x 4 entries that are only ever
-// 0 or 1) as dense double matrices and rolls them with chains of row swaps; run literally against HBM that is
-// thousands of dependent memory round trips per control iteration.  Here a matrix is four 64-bit column masks in
-// registers and in the persistent state (bit i = row i; the host getters unpack them), so
-// "row i is all zero", "roll rows 0..n" and the phase-duration scans are a few integer instructions.  The
+// The gait matrices are four 64-bit column masks (csrc/gait_masks.h, with the size rule that keeps every shift below 64); the
 // footstep table is produced row by row from registers and written once; the foot trajectory state is held in
 // statically indexed register arrays (the swing-feet list becomes a 4-bit mask).
-struct Gm {
-  unsigned long long c[4];
-};
-__device__ __forceinline__ unsigned long long gm_any(const Gm& m) { return m.c[0] | m.c[1] | m.c[2] | m.c[3]; }
-__device__ __forceinline__ bool rz(const Gm& m, int i) { return ((gm_any(m) >> i) & 1ull) == 0ull; }
-__device__ __forceinline__ bool gbit(const Gm& m, int i, int j) {
-  const unsigned long long col = (j == 0) ? m.c[0] : (j == 1) ? m.c[1] : (j == 2) ? m.c[2] : m.c[3];
-  return ((col >> i) & 1ull) != 0ull;
-}
-__device__ __forceinline__ unsigned long long lowmask(int n) { return (n >= 64) ? ~0ull : ((1ull << n) - 1ull); }
-// rows 0..n-1: new[r] = old[r+1] (r < n-1), new[n-1] = old[0]   (what "swap(0,1), swap(1,2), ..., swap(n-2,n-1)" does)
-__device__ __forceinline__ void rot_up(Gm& m, int n) {
-  if (n < 2) return;
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    const unsigned long long lo = m.c[c] & lowmask(n), hi = m.c[c] & ~lowmask(n);
-    m.c[c] = hi | (lo >> 1) | ((lo & 1ull) << (n - 1));
-  }
-}
-// rows 0..n-1: new[0] = old[n-1], new[r] = old[r-1]              ("swap(n-1,n-2), ..., swap(1,0)")
-__device__ __forceinline__ void rot_down(Gm& m, int n) {
-  if (n < 2) return;
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    const unsigned long long lo = m.c[c] & lowmask(n), hi = m.c[c] & ~lowmask(n);
-    m.c[c] = hi | ((lo << 1) & lowmask(n)) | ((lo >> (n - 1)) & 1ull);
-  }
-}
-__device__ __forceinline__ void rows_fill(Gm& m, int r0, int n, bool a, bool b, bool c, bool d) {
-  const unsigned long long f = lowmask(n) << r0;
-  if (a) m.c[0] |= f;
-  if (b) m.c[1] |= f;
-  if (c) m.c[2] |= f;
-  if (d) m.c[3] |= f;
-}
 __device__ __forceinline__ void gm_load(const PS& s, int item, Gm& m) {
 #pragma unroll
   for (int c = 0; c < 4; c++) m.c[c] = (unsigned long long)__double_as_longlong(s(item + c));
@@ -125,87 +86,6 @@ __device__ __forceinline__ void gm_load(const PS& s, int item, Gm& m) {
 __device__ __forceinline__ void gm_store(const PS& s, int item, const Gm& m) {
 #pragma unroll
   for (int c = 0; c < 4; c++) s(item + c) = __longlong_as_double((long long)m.c[c]);
-}
-
-// desired gait of one period (src/Gait.cpp:38-108); code 5 = walk (exists in the reference but is not reachable there)
-__device__ void create_desired(Gm& des, const PlannerArgs& a, int code) {
-  des.c[0] = des.c[1] = des.c[2] = des.c[3] = 0ull;
-  const int Nh = (int)lround(0.5 * a.T_gait / a.dt_mpc);
-  if (code == 1) { rows_fill(des, 0, Nh, 1, 0, 1, 0); rows_fill(des, Nh, Nh, 0, 1, 0, 1); }
-  else if (code == 2) { rows_fill(des, 0, Nh, 1, 1, 0, 0); rows_fill(des, Nh, Nh, 0, 0, 1, 1); }
-  else if (code == 3) { rows_fill(des, 0, Nh, 1, 0, 0, 1); rows_fill(des, Nh, Nh, 0, 1, 1, 0); }
-  else if (code == 4) { rows_fill(des, 0, (int)lround(a.T_gait / a.dt_mpc), 1, 1, 1, 1); }
-  else if (code == 5) {
-    const int Nq = (int)lround(0.25 * a.T_gait / a.dt_mpc);
-    rows_fill(des, 0, Nq, 0, 1, 1, 1); rows_fill(des, Nq, Nq, 1, 0, 1, 1);
-    rows_fill(des, 2 * Nq, Nq, 1, 1, 0, 1); rows_fill(des, 3 * Nq, Nq, 1, 1, 1, 0);
-  }
-}
-
-// Gait::initialize (src/Gait.cpp:19-36) + create_gait_f (:110-139)
-__device__ void gait_init(Gm& past, Gm& cur, Gm& des, const PlannerArgs& a) {
-  past.c[0] = past.c[1] = past.c[2] = past.c[3] = 0ull;
-  cur = past;
-  create_desired(des, a, 3);
-  int i = 0;
-  for (int j = 0; j < a.n_steps; j++) {
-#pragma unroll
-    for (int c = 0; c < 4; c++) cur.c[c] |= ((des.c[c] >> i) & 1ull) << j;
-    i++;
-    if (rz(des, i)) i = 0;
-  }
-  int index = 1;
-  while (!rz(des, index)) index++;
-  for (int k = 0; k < i; k++) rot_up(des, index);
-}
-
-// Gait::getPhaseDuration (src/Gait.cpp:141-182); also leaves remainingTime_.  The reference walks the rows one by one (forwards
-// through the current gait and on into the desired one, backwards through the current one and on into the past one); on column
-// masks each walk is "count the consecutive rows whose bit equals `value`" = a count of trailing / leading ones: no loop (round 4:
-// the loops' trip counts differ per lane, a wavefront paid the longest one, ~1 k instructions per call).
-__device__ __forceinline__ int trailing_ones(unsigned long long x) { return (~x == 0ull) ? 64 : (__ffsll((long long)~x) - 1); }
-__device__ double phase_duration(const Gm& past, const Gm& cur, const Gm& des, const PlannerArgs& a, int i, int j, bool value,
-                                 double& remain) {
-  const unsigned long long ccur = (j == 0) ? cur.c[0] : (j == 1) ? cur.c[1] : (j == 2) ? cur.c[2] : cur.c[3];
-  const unsigned long long cdes = (j == 0) ? des.c[0] : (j == 1) ? des.c[1] : (j == 2) ? des.c[2] : des.c[3];
-  const unsigned long long cpast = (j == 0) ? past.c[0] : (j == 1) ? past.c[1] : (j == 2) ? past.c[2] : past.c[3];
-  const unsigned long long vcur = value ? ccur : ~ccur, vdes = value ? cdes : ~cdes, vpast = value ? cpast : ~cpast;
-  const unsigned long long nzc = gm_any(cur);
-  // forwards: rows i + 1, i + 2, ... while the row is not all zero and the foot's entry equals `value` (:147-152)
-  const unsigned long long fwd = (i + 1 < 64) ? ((vcur & nzc) >> (i + 1)) : 0ull;
-  const int run = trailing_ones(fwd);
-  int cnt = 1 + run;
-  const int inext = i + run + 1;
-  if (inext >= 64 || ((nzc >> inext) & 1ull) == 0ull) cnt += trailing_ones(vdes & gm_any(des));  // the walk ran into the zero row: on into the desired gait (:154-162)
-  remain = (double)cnt;  // remainingTime_ (:164)
-  // backwards from the ORIGINAL row: rows i - 1, i - 2, ... while the entry equals `value` (no zero-row test, :167-171)
-  const unsigned long long miss = ~vcur & lowmask(i);  // rows below i whose entry differs
-  const int runb = (miss == 0ull) ? i : (i - 1 - (63 - __clzll((long long)miss)));
-  cnt += runb;
-  if (runb == i) cnt += trailing_ones(vpast & gm_any(past));  // reached row 0: on into the past gait (:173-180)
-  return (double)cnt * a.dt_mpc;
-}
-
-// Gait::updateGait = changeGait + rollGait (src/Gait.cpp:184-260); returns whether the gait matrices were rolled
-__device__ void gait_update(Gm& past, Gm& cur, Gm& des, const PlannerArgs& a, int k, int code, double& newphase) {
-  if (code >= 1 && code <= 5) create_desired(des, a, code);
-  if (k % a.k_mpc != 0) return;
-  rot_down(past, a.n_steps + 1);
-  bool differ = false;
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    past.c[c] = (past.c[c] & ~1ull) | (cur.c[c] & 1ull);
-    differ = differ || ((cur.c[c] & 1ull) != ((cur.c[c] >> 1) & 1ull));
-  }
-  newphase = differ ? 1.0 : 0.0;
-  int index = 1;
-  while (!rz(cur, index)) index++;
-  rot_up(cur, index);
-#pragma unroll
-  for (int c = 0; c < 4; c++) cur.c[c] = (cur.c[c] & ~(1ull << (index - 1))) | ((des.c[c] & 1ull) << (index - 1));
-  index = 1;
-  while (!rz(des, index)) index++;
-  rot_up(des, index);
 }
 
 // pinocchio::rpy::matrixToRpy of the rotation of quaternion (x, y, z, w) [third-party definition restated]
@@ -268,6 +148,18 @@ __device__ __forceinline__ double ipow(double x) {
 #pragma unroll
   for (int i = 1; i < N; i++) r *= x;
   return r;
+}
+
+// t0 of a foot whose swing is under way when the gait rolls (src/FootTrajectoryGenerator.cpp:122-124), every product and difference
+// rounded on its own as in the reference's build.  `t0 < t_swing - lock_time` (:53) decides whether the swing's coefficients follow
+// the moving target once more, and with durations that are multiples of dt_wbc it is an exact tie several times per swing: a
+// fused multiply-add here moved t0 by an ulp across the tie and the foot by a centimetre (tests/test_gpu_planner_params.py).
+__device__ __forceinline__ double swing_t0(double tsw, double remain, int k_mpc, int k, double dt_wbc) {
+#pragma clang fp contract(off)
+  const double steps = remain * k_mpc - ((k + 1) % k_mpc);
+  const double ahead = steps * dt_wbc;
+  const double value = tsw - ahead - dt_wbc;
+  return fmax(0.0, value);
 }
 
 // Foot trajectory state of one instance in registers (statically indexed: loops over the four feet are unrolled)
@@ -600,8 +492,7 @@ __device__ __forceinline__ void planner_body(const PlannerArgs& a, int b, long l
           const double tsw = phase_duration(past, cur, des, a, 0, i, false, remain);
           remain_dirty = true;
           f.tsw[i] = tsw;
-          const double value = tsw - (remain * a.k_mpc - ((k + 1) % a.k_mpc)) * a.dt_wbc - a.dt_wbc;
-          f.t0s[i] = fmax(0.0, value);
+          f.t0s[i] = swing_t0(tsw, remain, a.k_mpc, k, a.dt_wbc);
         }
     } else {
       const int nf = (int)nfeet_s;
@@ -1121,8 +1012,7 @@ __global__ __launch_bounds__(64) void control_pre_quad_kernel(ControllerArgs cu,
         const double tsw = phase_duration(past, cur, des, a, 0, j, false, remain);
         last_call = (double)(4 * Ng + j);
         ft.tsw = tsw;
-        const double value = tsw - (remain * a.k_mpc - ((k + 1) % a.k_mpc)) * a.dt_wbc - a.dt_wbc;
-        ft.t0s = fmax(0.0, value);
+        ft.t0s = swing_t0(tsw, remain, a.k_mpc, k, a.dt_wbc);
       }
     } else {
       const int nf = (int)nfeet_s;

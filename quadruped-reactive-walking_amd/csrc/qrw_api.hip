@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/qrw_solo12_model.h"
+#include "gait_masks.h"
 #include "kalman_filter.h"
 #include "qrw_host.h"
 
@@ -654,13 +655,19 @@ static qrw::PlannerArgs planner_step_args(qrw_handle h, int32_t k, const double*
   return a;
 }
 
+extern "C" int qrw_gait_table_fits(qrw_handle h) {  // (host arithmetic on the handle's configuration: no device is touched)
+  if (!h) return fail(-1, "qrw_gait_table_fits: null handle");
+  return qrw::gait_table_fits(h->cfg.N_gait, h->cfg.n_steps, h->cfg.T_gait, h->cfg.dt_mpc) ? 1 : 0;
+}
+
 extern "C" int qrw_planner_init(qrw_handle h, const qrw_planner_config* pc, void* stream) {
   QRW_ENTER(h, !pc, "qrw_planner_init: null argument");
   if (pc->k_mpc < 1) return fail(-1, "qrw_planner_init: k_mpc must be >= 1");
   if (h->cfg.N_gait > 63) return fail(-1, "qrw_planner_init: N_gait must be <= 63 (gait matrices are 64-bit column masks)");
-  // Gait::initialize throws when the matrices are too small (src/Gait.cpp:30-31)
-  const long per = lround(h->cfg.T_gait / h->cfg.dt_mpc);
-  if (h->cfg.n_steps > h->cfg.N_gait || per > h->cfg.N_gait || h->cfg.n_steps + 1 > h->cfg.N_gait)
+  // Gait::initialize throws when the matrices are too small (src/Gait.cpp:30-31).  The size rule of csrc/gait_masks.h -- every
+  // gait a code can select fits the table -- is tested HERE, ahead of the launch: the kernels' mask arithmetic relies on it
+  // (a table it refuses could keep their zero-row searches from ending) and does not test it again.
+  if (!qrw::gait_table_fits(h->cfg.N_gait, h->cfg.n_steps, h->cfg.T_gait, h->cfg.dt_mpc))
     return fail(-3, "Sizes of matrices are too small for considered durations. Increase N_gait in config file.");
   h->pcfg = *pc;
   qrw::PlannerArgs a;

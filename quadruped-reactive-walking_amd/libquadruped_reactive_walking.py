@@ -112,9 +112,11 @@ class QPWBC:
 class _PlannerCore:
     def __init__(self, dt, T_gait, T_mpc, N_gait):
         self.dt, self.T_gait, self.T_mpc, self.N_gait = float(dt), float(T_gait), float(T_mpc), int(N_gait)
-        self.n_steps = int(round(T_mpc / dt))
-        if self.n_steps > self.N_gait or int(round(T_gait / dt)) > self.N_gait or self.n_steps + 1 > self.N_gait:
-            # std::invalid_argument of Gait::initialize (src/Gait.cpp:30-31)
+        self.n_steps = qrw_hip.lround(self.T_mpc / self.dt)
+        if self.n_steps > self.N_gait:
+            # std::invalid_argument of Gait::initialize (src/Gait.cpp:30-31), its first condition: a table with fewer rows than the
+            # horizon has steps cannot even be allocated (qrw_create).  Every other table goes to the library's one size rule:
+            # qrw_planner_init returns -3, which Batch.planner_init raises as this same ValueError (_build below)
             raise ValueError("Sizes of matrices are too small for considered durations. Increase N_gait in config file.")
         self.cfg = dict(k_mpc=10, h_ref=0.2229, shoulders=qrw_hip.SHOULDERS.copy(), max_height=0.05, lock_time=0.07,
                         init_target=None, init_foot_pos=None, dt_wbc=0.002)
@@ -193,7 +195,7 @@ class StatePlanner:
         self._b = None
 
     def initialize(self, dt_in, T_mpc_in, h_ref_in):
-        n = int(round(T_mpc_in / dt_in))
+        n = qrw_hip.lround(float(T_mpc_in) / float(dt_in))
         self._n = n
         self._b = qrw_hip.Batch(1, n_steps=n, N_gait=n + 4, dt_mpc=float(dt_in), T_gait=float(T_mpc_in))
         self._b.planner_init(h_ref=float(h_ref_in))

@@ -9,6 +9,7 @@ stream); the *_host methods take/return numpy arrays and are what the single-rob
 classes (libquadruped_reactive_walking.py) use.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -125,6 +126,7 @@ SIGNATURES = {
     "qrw_fixed_feet_host": (C.c_int, [_vp] + [_dp] * 7),
     "qrw_get_base_inertia_diag": (C.c_int, [_vp, _dp]),
     "qrw_planner_init": (C.c_int, [_vp, _vp, _vp]),
+    "qrw_gait_table_fits": (C.c_int, [_vp]),
     "qrw_planner_step": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp]),
     "qrw_planner_call_host": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp,
@@ -248,6 +250,15 @@ class CuStream:
             self.close()
         except Exception:
             pass
+
+
+def lround(x):
+    """C's lround (halves away from zero), which is how the library turns a duration into a number of rows or steps; Python's
+    round() sends halves to the even neighbour."""
+    x = float(x)
+    f = math.floor(abs(x))
+    n = f + (1 if abs(x) - f >= 0.5 else 0)
+    return int(n) if x >= 0 else -int(n)
 
 
 def selftest_sweeps():
@@ -449,6 +460,14 @@ class Batch:
             raise ValueError(self._lib.qrw_last_error().decode())
         _check(rc, "qrw_planner_init")
         self.k_mpc = int(k_mpc)
+
+    def gait_table_fits(self):
+        """Whether planner_init would accept this handle's gait table (the size rule of include/qrw_hip.h, asked of the library:
+        there is no copy of it here); nothing is initialised or launched."""
+        rc = self._lib.qrw_gait_table_fits(self._handle)
+        if rc < 0:
+            _check(rc, "qrw_gait_table_fits")
+        return bool(rc)
 
     def planner_step(self, k, q7, hv, vref, code=0, out=None):
         """Device API: q7 (B,7) or the full q (B,19) of controller_update_state, hv (B,6), vref (B,6) CUDA float64; code int

@@ -1,0 +1,355 @@
+"""csrc/gait_masks.h -- the gait matrices as 64-bit column masks, the text planner_kernel.hip compiles -- checked on the CPU:
+
+* a stand-alone g++ program under AddressSanitizer and UBSan walks every table size and every period against the dense matrices
+  of oracle/planner_oracle.c (nothing here is loaded into Python);
+* the configurations at which the oracle used to write outside its matrices either refuse or run clean;
+* the compiler's resource report of the three kernels that include the header is the recorded one.
+
+The size rule (gait_masks.h, include/qrw_hip.h) is what makes the mask arithmetic safe: a table it refuses would set bit 63 of
+a mask and keep the kernels' zero-row searches from ending.  It is therefore tested HERE, where a refusal is a return value, and
+the GPU tests of the refusals (tests/test_gpu_planner_limits.py) rely on this test having passed."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "quadruped-reactive-walking_amd", "csrc")
+ORACLE = os.path.join(ROOT, "oracle")
+
+HOST_PROGRAM = r"""
+// csrc/gait_masks.h against the dense gait matrices of oracle/planner_oracle.c, and its primitives against row-by-row loops.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include "gait_masks.h"
+#include "qrw_oracle.h"
+using namespace qrw;
+
+struct Args { double T_gait, dt_mpc; int n_steps, k_mpc; };
+static unsigned long long rng_state = 88172645463325252ull;
+static unsigned long long rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
+static long fails = 0;
+#define CHECK(cond, ...) do { if (!(cond)) { if (fails < 20) { fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } fails++; } } while (0)
+
+// ---------------------------------------------------------------- part A: the primitives on arbitrary masks (rows 0..63, row 64 = zero)
+struct Dense { bool r[65][4]; };
+static Dense to_dense(const Gm& m) {
+  Dense d;
+  for (int i = 0; i < 65; i++) for (int j = 0; j < 4; j++) d.r[i][j] = i < 64 && ((m.c[j] >> i) & 1ull);
+  return d;
+}
+static bool same(const Gm& m, const Dense& d) {
+  for (int i = 0; i < 64; i++) for (int j = 0; j < 4; j++) if ((bool)((m.c[j] >> i) & 1ull) != d.r[i][j]) return false;
+  return true;
+}
+static bool dzero(const Dense& d, int i) { return i >= 64 || !(d.r[i][0] || d.r[i][1] || d.r[i][2] || d.r[i][3]); }
+static void dswap(Dense& d, int a, int b) { for (int j = 0; j < 4; j++) { bool t = d.r[a][j]; d.r[a][j] = d.r[b][j]; d.r[b][j] = t; } }
+// Gait::getPhaseDuration as the row-by-row walk it is, on 65-row matrices
+static int dense_phase(const Dense& past, const Dense& cur, const Dense& des, int i, int j, bool value, int& remain) {
+  int t = 1, a = i;
+  while (!dzero(cur, i + 1) && cur.r[i + 1][j] == value) { i++; t++; }
+  if (dzero(cur, i + 1)) { int k = 0; while (!dzero(des, k) && des.r[k][j] == value) { k++; t++; } }
+  remain = t;
+  while (a > 0 && cur.r[a - 1][j] == value) { a--; t++; }
+  if (a == 0) { while (!dzero(past, a) && past.r[a][j] == value) { a++; t++; } }
+  return t;
+}
+static Gm random_mask(int kind) {
+  Gm m;
+  for (int c = 0; c < 4; c++) {
+    unsigned long long x = rnd();
+    if (kind == 1) x &= rnd() & rnd();            // sparse: zero rows appear
+    if (kind == 2) x |= rnd() | rnd();            // dense: long runs
+    if (kind == 3) x = ~0ull;                     // every row of every foot set, bit 63 included
+    if (kind == 4) x = lowmask((int)(rnd() % 65));  // a block of live rows, up to all 64
+    if (kind == 5) x = (rnd() % 2) ? lowmask((int)(rnd() % 65)) : 0ull;
+    m.c[c] = x;
+  }
+  return m;
+}
+static long primitives() {
+  long n = 0;
+  const Args a{0.32, 0.02, 16, 10};
+  for (int n_ = 0; n_ <= 64; n_++) {
+    CHECK(lowmask(n_) == (n_ == 64 ? ~0ull : ((1ull << n_) - 1ull)), "lowmask %d", n_);
+    CHECK(trailing_ones(lowmask(n_)) == n_, "trailing_ones %d", n_);
+    CHECK(n_ >= 62 || trailing_ones(lowmask(n_) | (1ull << 63) | (1ull << (n_ + 1))) == n_, "trailing_ones with bits above the run %d", n_);
+  }
+  for (int rep = 0; rep < 300; rep++)
+    for (int kind = 0; kind < 6; kind++) {
+      const Gm m0 = random_mask(kind);
+      for (int rows = 0; rows <= 64; rows += (rep % 3) + 1) {
+        Gm u = m0, d = m0;
+        Dense du = to_dense(m0), dd = to_dense(m0);
+        rot_up(u, rows);
+        for (int r = 0; r + 1 < rows; r++) dswap(du, r, r + 1);
+        rot_down(d, rows);
+        for (int r = rows - 1; r > 0; r--) dswap(dd, r, r - 1);
+        CHECK(same(u, du), "rot_up %d", rows);
+        CHECK(same(d, dd), "rot_down %d", rows);
+        n += 2;
+      }
+      {
+        const int r0 = (int)(rnd() % 64), cnt = (int)(rnd() % (65 - r0));
+        const bool f[4] = {(bool)(rnd() & 1), (bool)(rnd() & 1), (bool)(rnd() & 1), (bool)(rnd() & 1)};
+        Gm w = m0;
+        Dense dw = to_dense(m0);
+        rows_fill(w, r0, cnt, f[0], f[1], f[2], f[3]);
+        for (int r = r0; r < r0 + cnt; r++) for (int j = 0; j < 4; j++) dw.r[r][j] = dw.r[r][j] || f[j];
+        CHECK(same(w, dw), "rows_fill %d %d", r0, cnt);
+        n++;
+      }
+      const Gm past = random_mask((kind + rep) % 6), des = random_mask((kind + 2 * rep + 1) % 6);
+      const Dense dp = to_dense(past), dc = to_dense(m0), dds = to_dense(des);
+      for (int i = 0; i < 64; i++) {
+        CHECK(rz(m0, i) == dzero(dc, i), "rz %d", i);
+        for (int j = 0; j < 4; j++) {
+          CHECK(gbit(m0, i, j) == dc.r[i][j], "gbit %d %d", i, j);
+          for (int v = 0; v < 2; v++) {
+            double rem = -1.0;
+            int drem = -1;
+            const double t = phase_duration(past, m0, des, a, i, j, v != 0, rem);
+            const int dt_ = dense_phase(dp, dc, dds, i, j, v != 0, drem);
+            CHECK(t == (double)dt_ * a.dt_mpc && rem == (double)drem, "phase_duration kind %d i %d j %d v %d: %g %g, dense %d %d", kind, i, j, v, t / a.dt_mpc, rem, dt_, drem);
+            n++;
+          }
+        }
+      }
+    }
+  return n;
+}
+
+// ---------------------------------------------------------------- part B: every table, every period, against the dense oracle
+static const double kSh[12] = {0.1946, 0.1946, -0.1946, -0.1946, 0.14695, -0.14695, 0.14695, -0.14695, 0.0, 0.0, 0.0, 0.0};
+static const double kQ7[7] = {0.0, 0.0, 0.2229, 0.0, 0.0, 0.0, 1.0};
+
+static void compare_matrices(planner_oracle* o, int Ng, const Gm& past, const Gm& cur, const Gm& des, const char* what, int k) {
+  double dp[63 * 4], dc[63 * 4], dd[63 * 4];
+  planner_oracle_get_gaits(o, dp, dc, dd);
+  const Gm* m[3] = {&past, &cur, &des};
+  const double* d[3] = {dp, dc, dd};
+  for (int w = 0; w < 3; w++) {
+    for (int i = 0; i < Ng; i++)
+      for (int j = 0; j < 4; j++) CHECK((gbit(*m[w], i, j) ? 1.0 : 0.0) == d[w][i * 4 + j], "%s k %d matrix %d row %d foot %d (N_gait %d)", what, k, w, i, j, Ng);
+    CHECK((gm_any(*m[w]) & ~lowmask(Ng)) == 0ull, "%s k %d matrix %d has a bit at or above row N_gait %d", what, k, w, Ng);
+  }
+}
+static void compare_phases(planner_oracle* o, const Args& a, const Gm& past, const Gm& cur, const Gm& des, int k) {
+  int live = 0;
+  while (!rz(cur, live)) live++;
+  if (live == 0) return;  // (an empty current gait: a period of one row and the walk, whose generator then writes no row at all)
+  const int rows[5] = {0, live > 1 ? 1 : 0, live - 1, (int)(rnd() % (unsigned)live), (int)(rnd() % (unsigned)live)};
+  for (int r = 0; r < 5; r++)
+    for (int j = 0; j < 4; j++)
+      for (int v = 0; v < 2; v++) {
+        double rem = -1.0, fl[4];
+        const double t = phase_duration(past, cur, des, a, rows[r], j, v != 0, rem);
+        const double to = planner_oracle_phase_duration(o, rows[r], j, (double)v);
+        planner_oracle_get_flags(o, fl);
+        CHECK(t == to && rem == fl[2], "phase_duration k %d row %d foot %d value %d: %.17g rem %g, oracle %.17g rem %g", k, rows[r], j, v, t, rem, to, fl[2]);
+      }
+}
+
+// the two rules off the grid below: periods with halves in them, sizes at and beyond the limits, durations that are no durations
+static void rules_off_the_grid() {
+  const int Ns[] = {0, 1, 2, 5, 9, 17, 18, 20, 62, 63, 64, 70}, steps[] = {0, 1, 4, 16, 17, 32};
+  const double nan = __builtin_nan(""), inf = __builtin_inf();
+  const double Td[][2] = {{0.32, 0.02}, {0.36, 0.02}, {0.30, 0.02}, {0.40, 0.02}, {1.24, 0.02}, {1.26, 0.02}, {0.625, 0.25}, {2.25, 0.5},
+                          {-1.0, 0.02}, {nan, 0.02}, {1e300, 0.02}, {inf, 0.02}, {0.32, 0.0}, {0.0, 0.0}, {0.32, nan}};
+  int yes = 0, no = 0;
+  for (int N : Ns) for (int n : steps) for (auto& td : Td) {
+    const bool fits = gait_table_fits(N, n, td[0], td[1]);
+    CHECK(fits == (planner_oracle_table_fits(N, n, td[0], td[1]) != 0), "the two rules differ at N_gait %d n_steps %d T_gait %g dt %g", N, n, td[0], td[1]);
+    CHECK(gait_rows_needed(td[0], td[1]) == planner_oracle_rows_needed(td[0], td[1]), "rows needed differ at T_gait %g dt %g", td[0], td[1]);
+    (fits ? yes : no)++;
+  }
+  CHECK(yes > 0 && no > 0, "rules_off_the_grid: %d accepted, %d refused", yes, no);
+  CHECK(gait_rows_needed(2.25, 0.5) == 5 && gait_rows_needed(0.625, 0.25) == 4, "halves round up");
+}
+
+int main() {
+  const long nprim = primitives();
+  rules_off_the_grid();
+  long ran = 0, refused = 0, updates = 0;
+  const double dt = 0.02;
+  for (int Ng = 2; Ng <= 63; Ng++)
+    for (int rows = 1; rows <= Ng; rows++) {
+      static const int grid[8][2] = {{1, 1}, {1, 4}, {4, 1}, {4, 4}, {16, 1}, {16, 4}, {32, 1}, {32, 4}};  // (n_steps, k_mpc)
+      for (int g = 0; g < 8; g++) {
+        const Args a{rows * dt, dt, grid[g][0], grid[g][1]};
+        const bool fits = gait_table_fits(Ng, a.n_steps, a.T_gait, a.dt_mpc);
+        CHECK(fits == (planner_oracle_table_fits(Ng, a.n_steps, a.T_gait, a.dt_mpc) != 0), "the two rules differ at N_gait %d rows %d n_steps %d", Ng, rows, a.n_steps);
+        const int need = gait_rows_needed(a.T_gait, a.dt_mpc);
+        CHECK(need == planner_oracle_rows_needed(a.T_gait, a.dt_mpc) && need >= rows && need <= rows + 3, "rows needed %d for %d rows", need, rows);
+        planner_oracle* o = planner_oracle_create(dt, 0.002, a.T_gait, a.n_steps * dt, Ng, a.k_mpc, 0.2229, kSh, 0.05, 0.07, kSh, kSh);
+        CHECK(fits == (o != nullptr), "oracle %s where the rule %s: N_gait %d rows %d n_steps %d", o ? "accepts" : "refuses", fits ? "accepts" : "refuses", Ng, rows, a.n_steps);
+        if (!fits || !o) { refused++; if (o) planner_oracle_destroy(o); continue; }
+        // every generator stays inside the table: nothing at or above row N_gait, so never bit 63
+        for (int code = 1; code <= 5; code++) {
+          Gm t;
+          create_desired(t, a, code);
+          CHECK((gm_any(t) & ~lowmask(Ng)) == 0ull, "code %d writes beyond row N_gait %d (rows %d)", code, Ng, rows);
+        }
+        Gm past, cur, des;
+        double newphase = 0.0;
+        gait_init(past, cur, des, a);
+        compare_matrices(o, Ng, past, cur, des, "init", -1);
+        // the code schedule, in rolls (a roll every k_mpc iterations): two codes on consecutive rolls, a code while the transition
+        // they started is still going on, static, away from static (to the walk), code 0 in between, a code on an iteration that
+        // does not roll, and at least two of the longest periods (`need` rows) after the last one
+        const int P = need, K = a.k_mpc;
+        const int ev_roll[7] = {2, 3, 5, 6 + P, 9 + P, 11 + 2 * P, 12 + 2 * P};
+        const int ev_code[7] = {1, 2, 3, 4, 5, 2, 3};
+        const int last = (ev_roll[6] + 2 * P + a.n_steps + 2) * K;
+        for (int k = 0; k < last; k++) {
+          int code = 0;
+          for (int e = 0; e < 7; e++)
+            if (k == ev_roll[e] * K + ((e == 2 || e == 5) && K > 1 ? 1 : 0)) code = ev_code[e];
+          gait_update(past, cur, des, a, k, code, newphase);
+          planner_oracle_gait_update(o, k, kQ7, code);
+          updates++;
+          if (code != 0 || k % K == 0) {
+            double fl[4];
+            planner_oracle_get_flags(o, fl);
+            CHECK(newphase == fl[0], "newPhase k %d: %g, oracle %g (N_gait %d rows %d n_steps %d k_mpc %d)", k, newphase, fl[0], Ng, rows, a.n_steps, K);
+            compare_matrices(o, Ng, past, cur, des, "update", k);
+            compare_phases(o, a, past, cur, des, k);
+          }
+          if (fails) break;
+        }
+        planner_oracle_destroy(o);
+        ran++;
+        if (fails) { fprintf(stderr, "stopped at N_gait %d rows %d n_steps %d k_mpc %d\n", Ng, rows, a.n_steps, K); return 1; }
+      }
+    }
+  printf("primitive checks %ld, configurations run %ld, refused %ld, gait updates %ld\n", nprim, ran, refused, updates);
+  return fails ? 1 : 0;
+}
+"""
+
+
+def test_gait_masks_against_the_dense_oracle_under_the_sanitizers(tmp_path):
+    """csrc/gait_masks.h and oracle/planner_oracle.c in one stand-alone program under -fsanitize=address,undefined.
+
+    Part A: lowmask, trailing_ones, rot_up, rot_down, rows_fill, rz, gbit and phase_duration on arbitrary 64-bit masks -- sparse,
+    dense, all ones, blocks up to all 64 rows -- against row-by-row loops on 65-row dense matrices (row 64 zero): phase_duration
+    is defined for every mask, bit 63 included, and UBSan would see a shift by 64.
+    Part B: every N_gait in 2..63 x every period of 1..N_gait rows x n_steps in {1, 4, 16, 32} x k_mpc in {1, 4}.  Where the size rule refuses, the oracle refuses too; where it accepts, no generator writes at or above row N_gait,
+    and a schedule of codes (consecutive, during a transition, static and away again, on a non-rolling iteration) runs to two
+    of the longest periods past the last code with the three matrices, newPhase, and phase_duration + remainingTime (row 0, row
+    1, the last live row and two random live rows, four feet, both values) equal to the dense oracle's after every update."""
+    if shutil.which("g++") is None or shutil.which("gcc") is None:
+        pytest.skip("g++ / gcc not available")
+    src, obj, exe = tmp_path / "gait_host.cpp", tmp_path / "planner_oracle.o", tmp_path / "gait_host"
+    src.write_text(HOST_PROGRAM)
+    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+    r = subprocess.run(["gcc", "-std=gnu99", "-ffp-contract=off", "-Wall", "-Wextra", "-Wno-unused-parameter"] + san +
+                       ["-I" + ORACLE, "-c", os.path.join(ORACLE, "planner_oracle.c"), "-o", str(obj)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"] + san +
+                       ["-I" + CSRC, "-I" + ORACLE, str(src), str(obj), "-lm", "-o", str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    print(r.stdout.strip())
+    assert r.returncode == 0 and r.stderr.strip() == "", (r.returncode, r.stderr[-3000:])
+    m = re.fullmatch(r"primitive checks (\d+), configurations run (\d+), refused (\d+), gait updates (\d+)", r.stdout.strip())
+    assert m, r.stdout[-500:]
+    nprim, ran, refused, updates = (int(x) for x in m.groups())
+    assert ran + refused == 8 * sum(range(2, 64)) and ran > 10000 and refused > 1000 and nprim > 500000, r.stdout
+
+
+# the probes that used to end in glibc aborts ("corrupted size vs. prev_size") or in silent writes beyond the matrices
+PROBES = [  # N_gait, T_gait, codes, accepted
+    (63, 1.24, (1, 2, 3, 4), False),  # 62 rows; the walk would write 64
+    (63, 1.24, (5,), False),
+    (63, 1.26, (3,), False),          # 63 rows; the trot would write 64
+    (20, 0.40, (1, 2, 3, 4), True),   # 20 rows = N_gait: the full table, legal
+    (20, 0.36, (5,), True),           # 18 rows; the walk writes 20 and fills the table
+    (16, 0.30, (1, 2, 3), False),     # 15 rows; the trot writes 16 -- fits 16 rows, but n_steps + 1 = 17 does not
+    (20, 0.30, (1, 2, 3), True),      # 15 rows with a 16-row trot
+]
+
+
+@pytest.mark.parametrize("N_gait,T_gait,codes,accepted", PROBES)
+def test_probes_that_used_to_abort_refuse_or_run_clean(oracle_mod, N_gait, T_gait, codes, accepted):
+    """oracle.Planner(k_mpc=4, T_mpc=0.32) at the table's limits for 800 iterations with a code every 97: refused by the size rule
+    (ValueError, as the device's -3), or run to the end with every matrix entry 0 or 1, the live rows inside the table and the
+    number of live rows of the current gait constant (a roll takes one row and adds one)."""
+    if not accepted:
+        assert not oracle_mod.load().planner_oracle_table_fits(N_gait, 16, T_gait, 0.02)
+        with pytest.raises(ValueError):
+            oracle_mod.Planner(k_mpc=4, N_gait=N_gait, T_gait=T_gait, T_mpc=0.32)
+        return
+    p = oracle_mod.Planner(k_mpc=4, N_gait=N_gait, T_gait=T_gait, T_mpc=0.32)
+    q7 = np.array([0.0, 0.0, 0.2229, 0.0, 0.0, 0.0, 1.0])
+    v = np.array([0.3, 0.05, 0, 0, 0, 0.2])
+    n = 0
+    for k in range(800):
+        code = 0
+        if k % 97 == 96:
+            code = codes[n % len(codes)]
+            n += 1
+        p.step(k, q7, v, v, code)
+        past, cur, des = p.gaits()
+        for m in (past, cur, des):
+            assert np.isin(m, (0.0, 1.0)).all(), k
+        assert np.count_nonzero(cur.any(axis=1)) == 16 and cur[:16].any(axis=1).all(), k
+        assert np.isfinite(p.footsteps()[0]).all() and np.isfinite(p.xref()).all() and all(np.isfinite(x).all() for x in p.feet()), k
+
+
+def test_rule_is_one_rule(oracle_mod):
+    """The oracle's rule on periods that have halves in them (T_gait / dt_mpc = 2.5, 4.5, ...: lround sends them up, Python's
+    round() to the even neighbour) -- the stand-alone program above holds the library's rule against it on these same values --
+    and the drop-in Gait class refusing, without a handle, a table with fewer rows than the horizon has steps."""
+    import libquadruped_reactive_walking as lqrw
+    import qrw_hip
+
+    lib = oracle_mod.load()
+    with pytest.raises(ValueError, match="Sizes of matrices are too small"):
+        lqrw.Gait().initialize(0.02, 0.32, 0.32, 10)  # (n_steps 16 in 10 rows, src/Gait.cpp:30-31)
+    assert qrw_hip.lround(2.5) == 3 and qrw_hip.lround(0.5) == 1 and qrw_hip.lround(-2.5) == -3 and qrw_hip.lround(2.4999) == 2
+    # 2.25 / 0.5 = 4.5 rows: lround gives 5, the trot writes 2 * lround(2.25) = 4, the walk 4 * lround(1.125) = 4 -> 5 rows needed
+    assert lib.planner_oracle_rows_needed(2.25, 0.5) == 5 and lib.planner_oracle_table_fits(5, 1, 2.25, 0.5) and not lib.planner_oracle_table_fits(4, 1, 2.25, 0.5)
+    assert lib.planner_oracle_rows_needed(0.625, 0.25) == 4  # 2.5 rows: lround 3, the trot 2 * lround(1.25) = 2, the walk 4 * lround(0.625) = 4
+    assert lib.planner_oracle_rows_needed(0.36, 0.02) == 20 and lib.planner_oracle_rows_needed(0.30, 0.02) == 16
+    assert lib.planner_oracle_rows_needed(1.24, 0.02) == 64 and lib.planner_oracle_rows_needed(1.22, 0.02) == 62
+    for T, dt in ((-1.0, 0.02), (float("nan"), 0.02), (1e300, 0.02), (0.32, 0.0)):
+        assert not lib.planner_oracle_table_fits(63, 16, T, dt), (T, dt)
+
+
+# ------------------------------------------------------------------------------------------------ resource report
+RECORDED = {  # DESIGN.md (planner section): the same figures before and after the mask arithmetic moved into gait_masks.h
+    "planner_kernel": dict(vgprs=256, agprs=124, scratch=0, spill=0),
+    "control_pre_kernel": dict(vgprs=256, agprs=128, scratch=0, spill=0),
+    "control_pre_quad_kernel": dict(vgprs=256, agprs=64, scratch=0, spill=0),
+}
+
+
+def test_planner_kernels_keep_their_resource_report(tmp_path):
+    """The compiler's own resource report (-Rpass-analysis=kernel-resource-usage) of planner_kernel.hip for gfx950: VGPRs, AGPRs,
+    scratch bytes and spilled vector registers of the three kernels that compile gait_masks.h are the figures recorded for the
+    commit before the header existed, none worse."""
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc not available")
+    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-pass-failed",
+                        "-Rpass-analysis=kernel-resource-usage", os.path.join(CSRC, "planner_kernel.hip"), "-o", str(tmp_path / "planner.s")],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    seen = {}
+    for part in r.stderr.split("Function Name: ")[1:]:
+        m = re.match(r"_ZN3qrw\d+(\w+?)E(?:NS_|v)", part.splitlines()[0])
+        if not m:
+            continue
+        seen[m.group(1)] = {key: int(re.search(pat + r": (\d+)", part).group(1))
+                            for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]"), ("spill", r"VGPRs Spill"), ("vgprs", r" VGPRs"),
+                                             ("agprs", r"AGPRs"))}
+    for name, s in sorted(seen.items()):
+        print("%s: %d VGPRs, %d AGPRs, scratch %d, spilled %d" % (name, s["vgprs"], s["agprs"], s["scratch"], s["spill"]))
+    assert sorted(seen) == sorted(RECORDED), sorted(seen)
+    for name, want in RECORDED.items():
+        for key, v in want.items():
+            assert seen[name][key] == v, (name, key, seen[name][key], v)

@@ -606,7 +606,7 @@ def test_staggered_stream_groups_equal_single_handles_started_late(free, default
         assert torch.equal(flags[sl], one.error_flag)
 
 
-@pytest.mark.parametrize("cfg", ["default", "alt", "short_period"])
+@pytest.mark.parametrize("cfg", ["default", "alt", "short_period", "full20", "wide"])
 def test_control_pre_quad_form_equals_the_thread_form_through_gait_changes(cfg, monkeypatch):
     """qrw_control_pre's quad kernel (one quad per robot: touch-downs of the footstep table computed wave-together, mask arithmetic
     for getPhaseDuration) against the one-thread-per-robot form (QRW_PRE_QUAD=0, the kernel the planner parity tests compare with
@@ -620,8 +620,12 @@ def test_control_pre_quad_form_equals_the_thread_form_through_gait_changes(cfg, 
         B, N, kw, k_mpc = 21, 16, dict(), 10
     elif cfg == "alt":  # 0.40 s gait on a 0.24 s horizon, 26 gait rows, 1 kHz loop
         B, N, kw, k_mpc = 21, 12, dict(N_gait=26, T_gait=0.40, dt_wbc=0.001), 20
-    else:  # a 0.08 s gait period in 24 rows: up to six touch-downs per foot in the table (the quad form's row-wise fallback)
+    elif cfg == "short_period":  # a 0.08 s gait period in 24 rows: up to six touch-downs per foot in the table (the quad form's row-wise fallback)
         B, N, kw, k_mpc = 21, 4, dict(N_gait=24, T_gait=0.08), 10
+    elif cfg == "full20":  # a 0.40 s period in 20 rows: the period fills the gait table (tests/planner_cases.py)
+        B, N, kw, k_mpc = 21, 16, dict(N_gait=20, T_gait=0.40), 10
+    else:  # "wide": 63 rows, a 1.22 s period (61 rows, a 62-row trot: masks up to bit 61), a 32-step horizon, k_mpc 4
+        B, N, kw, k_mpc = 21, 32, dict(N_gait=63, T_gait=1.22, dt_wbc=0.005), 4
     Ng = kw.get("N_gait", 20)
     rng = np.random.default_rng(77)
     engs = [qrw_hip.Batch(B, N, **kw) for _ in range(2)]
