@@ -35,6 +35,12 @@ CASES = {
     "odd": _case(N=12, T_gait=0.30, seq="limits"),                          # 15 rows, the trot writes 2 * 8 = 16
     "wide": _case(N=32, N_gait=63, T_gait=1.22, seq="limits", **_T4),       # 61 rows, a 62-row trot, a 33-row past gait
     "tight": _case(N=8, N_gait=9, T_gait=0.16, seq="limits"),               # 8 rows in 9, n_steps + 1 = N_gait
+    # ---- off the 0.02 s MPC step (k_mpc * dt_wbc = dt_mpc; neither T_gait nor dt_mpc is a binary fraction: lround sees quotients computed from rounded operands)
+    "step10": _case(N=16, N_gait=24, T_gait=0.20, dt_mpc=0.010, k_mpc=5, seq="limits"),                 # 20 rows per period
+    "step40": _case(N=8, N_gait=20, T_gait=0.48, dt_mpc=0.040, k_mpc=20, seq="limits"),                 # 12 rows
+    "step16": _case(N=20, N_gait=24, T_gait=0.32, dt_mpc=0.016, k_mpc=8, seq="limits"),                 # 20 rows
+    "step24": _case(N=12, N_gait=20, T_gait=0.36, dt_mpc=0.024, k_mpc=12, seq="limits"),                # 15 rows, trot and walk write 16
+    "step25": _case(N=12, N_gait=20, T_gait=0.40, dt_mpc=0.025, k_mpc=5, dt_wbc=0.005, seq="limits"),   # 16 rows
     # ---- off the default geometry
     "TUNED": _case(seq="tuned", iters=400, **_T4,
                    geometry=dict(shoulders=TUNED_SHOULDERS, h_ref=0.24, max_height=0.08, lock_time=0.04,
@@ -56,6 +62,7 @@ CASES = {
 }
 ALONE = ("shoulders", "h_ref", "max_height", "lock_time", "init_target", "init_foot_pos")
 LIMITS = ("full20", "walk_fills", "odd", "wide", "tight")
+STEPS = ("step10", "step40", "step16", "step24", "step25")
 
 
 def lround(x):
@@ -238,6 +245,11 @@ SPREAD = {
     "odd": dict(xref=2.22e-16, fsteps=2.50e-16, target=4.18e-16, pos=3.38e-11, vel=3.96e-10, acc=1.30e-08),  # 671 iterations x 9 robots
     "wide": dict(xref=3.05e-16, fsteps=4.72e-16, target=4.44e-16, pos=6.93e-08, vel=1.50e-07, acc=4.11e-07),  # 973 iterations x 9 robots
     "tight": dict(xref=2.22e-16, fsteps=1.11e-15, target=1.11e-15, pos=1.25e-12, vel=2.18e-11, acc=2.62e-10),  # 391 iterations x 9 robots
+    "step10": dict(xref=2.22e-16, fsteps=1.67e-16, target=2.22e-16, pos=2.06e-12, vel=2.03e-11, acc=2.91e-10),  # 456 iterations x 9 robots
+    "step40": dict(xref=2.22e-16, fsteps=5.00e-16, target=4.29e-16, pos=1.24e-09, vel=2.51e-09, acc=8.38e-09),  # 961 iterations x 9 robots
+    "step16": dict(xref=4.44e-16, fsteps=1.17e-15, target=1.22e-15, pos=2.23e-11, vel=2.47e-10, acc=5.82e-09),  # 669 iterations x 9 robots
+    "step24": dict(xref=1.11e-16, fsteps=2.00e-15, target=2.11e-15, pos=2.37e-10, vel=1.51e-09, acc=1.91e-08),  # 785 iterations x 9 robots
+    "step25": dict(xref=2.22e-16, fsteps=5.00e-16, target=5.36e-16, pos=9.07e-10, vel=6.96e-09, acc=5.36e-08),  # 386 iterations x 9 robots
     "TUNED": dict(xref=3.13e-16, fsteps=1.22e-15, target=1.22e-15, pos=2.88e-09, vel=3.47e-08, acc=1.62e-07),  # 400 iterations x 9 robots
     "base": dict(xref=2.22e-16, fsteps=5.55e-16, target=4.44e-16, pos=6.66e-11, vel=4.84e-10, acc=2.97e-09),  # 300 iterations x 9 robots
     "shoulders": dict(xref=2.22e-16, fsteps=5.00e-16, target=4.44e-16, pos=3.93e-11, vel=3.49e-10, acc=2.56e-09),  # 300 iterations x 9 robots

@@ -171,62 +171,85 @@ static void rules_off_the_grid() {
   CHECK(gait_rows_needed(2.25, 0.5) == 5 && gait_rows_needed(0.625, 0.25) == 4, "halves round up");
 }
 
+static long ran = 0, refused = 0, updates = 0;
+
+// one table (N_gait rows) at one configuration: the two rules, the generators, and the code schedule against the dense oracle.
+// rows: the period's length in rows as the caller means it (T_gait = rows * dt_mpc computed in floating point, or a literal).
+static bool one_configuration(int Ng, int rows, const Args& a, double dt_wbc) {
+  const double dt = a.dt_mpc;
+  const bool fits = gait_table_fits(Ng, a.n_steps, a.T_gait, a.dt_mpc);
+  CHECK(fits == (planner_oracle_table_fits(Ng, a.n_steps, a.T_gait, a.dt_mpc) != 0), "the two rules differ at N_gait %d rows %d n_steps %d dt %g", Ng, rows, a.n_steps, dt);
+  const int need = gait_rows_needed(a.T_gait, a.dt_mpc);
+  CHECK(need == planner_oracle_rows_needed(a.T_gait, a.dt_mpc) && need >= rows && need <= rows + 3, "rows needed %d for %d rows (dt %g)", need, rows, dt);
+  planner_oracle* o = planner_oracle_create(dt, dt_wbc, a.T_gait, a.n_steps * dt, Ng, a.k_mpc, 0.2229, kSh, 0.05, 0.07, kSh, kSh);
+  CHECK(fits == (o != nullptr), "oracle %s where the rule %s: N_gait %d rows %d n_steps %d dt %g", o ? "accepts" : "refuses", fits ? "accepts" : "refuses", Ng, rows, a.n_steps, dt);
+  if (!fits || !o) { refused++; if (o) planner_oracle_destroy(o); return true; }
+  // every generator stays inside the table: nothing at or above row N_gait, so never bit 63
+  for (int code = 1; code <= 5; code++) {
+    Gm t;
+    create_desired(t, a, code);
+    CHECK((gm_any(t) & ~lowmask(Ng)) == 0ull, "code %d writes beyond row N_gait %d (rows %d)", code, Ng, rows);
+  }
+  Gm past, cur, des;
+  double newphase = 0.0;
+  gait_init(past, cur, des, a);
+  compare_matrices(o, Ng, past, cur, des, "init", -1);
+  // the code schedule, in rolls (a roll every k_mpc iterations): two codes on consecutive rolls, a code while the transition
+  // they started is still going on, static, away from static (to the walk), code 0 in between, a code on an iteration that
+  // does not roll, and at least two of the longest periods (`need` rows) after the last one
+  const int P = need, K = a.k_mpc;
+  const int ev_roll[7] = {2, 3, 5, 6 + P, 9 + P, 11 + 2 * P, 12 + 2 * P};
+  const int ev_code[7] = {1, 2, 3, 4, 5, 2, 3};
+  const int last = (ev_roll[6] + 2 * P + a.n_steps + 2) * K;
+  for (int k = 0; k < last; k++) {
+    int code = 0;
+    for (int e = 0; e < 7; e++)
+      if (k == ev_roll[e] * K + ((e == 2 || e == 5) && K > 1 ? 1 : 0)) code = ev_code[e];
+    gait_update(past, cur, des, a, k, code, newphase);
+    planner_oracle_gait_update(o, k, kQ7, code);
+    updates++;
+    if (code != 0 || k % K == 0) {
+      double fl[4];
+      planner_oracle_get_flags(o, fl);
+      CHECK(newphase == fl[0], "newPhase k %d: %g, oracle %g (N_gait %d rows %d n_steps %d k_mpc %d)", k, newphase, fl[0], Ng, rows, a.n_steps, K);
+      compare_matrices(o, Ng, past, cur, des, "update", k);
+      compare_phases(o, a, past, cur, des, k);
+    }
+    if (fails) break;
+  }
+  planner_oracle_destroy(o);
+  ran++;
+  if (fails) { fprintf(stderr, "stopped at N_gait %d rows %d n_steps %d k_mpc %d dt %g\n", Ng, rows, a.n_steps, K, dt); return false; }
+  return true;
+}
+
 int main() {
   const long nprim = primitives();
   rules_off_the_grid();
-  long ran = 0, refused = 0, updates = 0;
   const double dt = 0.02;
   for (int Ng = 2; Ng <= 63; Ng++)
     for (int rows = 1; rows <= Ng; rows++) {
       static const int grid[8][2] = {{1, 1}, {1, 4}, {4, 1}, {4, 4}, {16, 1}, {16, 4}, {32, 1}, {32, 4}};  // (n_steps, k_mpc)
-      for (int g = 0; g < 8; g++) {
-        const Args a{rows * dt, dt, grid[g][0], grid[g][1]};
-        const bool fits = gait_table_fits(Ng, a.n_steps, a.T_gait, a.dt_mpc);
-        CHECK(fits == (planner_oracle_table_fits(Ng, a.n_steps, a.T_gait, a.dt_mpc) != 0), "the two rules differ at N_gait %d rows %d n_steps %d", Ng, rows, a.n_steps);
-        const int need = gait_rows_needed(a.T_gait, a.dt_mpc);
-        CHECK(need == planner_oracle_rows_needed(a.T_gait, a.dt_mpc) && need >= rows && need <= rows + 3, "rows needed %d for %d rows", need, rows);
-        planner_oracle* o = planner_oracle_create(dt, 0.002, a.T_gait, a.n_steps * dt, Ng, a.k_mpc, 0.2229, kSh, 0.05, 0.07, kSh, kSh);
-        CHECK(fits == (o != nullptr), "oracle %s where the rule %s: N_gait %d rows %d n_steps %d", o ? "accepts" : "refuses", fits ? "accepts" : "refuses", Ng, rows, a.n_steps);
-        if (!fits || !o) { refused++; if (o) planner_oracle_destroy(o); continue; }
-        // every generator stays inside the table: nothing at or above row N_gait, so never bit 63
-        for (int code = 1; code <= 5; code++) {
-          Gm t;
-          create_desired(t, a, code);
-          CHECK((gm_any(t) & ~lowmask(Ng)) == 0ull, "code %d writes beyond row N_gait %d (rows %d)", code, Ng, rows);
-        }
-        Gm past, cur, des;
-        double newphase = 0.0;
-        gait_init(past, cur, des, a);
-        compare_matrices(o, Ng, past, cur, des, "init", -1);
-        // the code schedule, in rolls (a roll every k_mpc iterations): two codes on consecutive rolls, a code while the transition
-        // they started is still going on, static, away from static (to the walk), code 0 in between, a code on an iteration that
-        // does not roll, and at least two of the longest periods (`need` rows) after the last one
-        const int P = need, K = a.k_mpc;
-        const int ev_roll[7] = {2, 3, 5, 6 + P, 9 + P, 11 + 2 * P, 12 + 2 * P};
-        const int ev_code[7] = {1, 2, 3, 4, 5, 2, 3};
-        const int last = (ev_roll[6] + 2 * P + a.n_steps + 2) * K;
-        for (int k = 0; k < last; k++) {
-          int code = 0;
-          for (int e = 0; e < 7; e++)
-            if (k == ev_roll[e] * K + ((e == 2 || e == 5) && K > 1 ? 1 : 0)) code = ev_code[e];
-          gait_update(past, cur, des, a, k, code, newphase);
-          planner_oracle_gait_update(o, k, kQ7, code);
-          updates++;
-          if (code != 0 || k % K == 0) {
-            double fl[4];
-            planner_oracle_get_flags(o, fl);
-            CHECK(newphase == fl[0], "newPhase k %d: %g, oracle %g (N_gait %d rows %d n_steps %d k_mpc %d)", k, newphase, fl[0], Ng, rows, a.n_steps, K);
-            compare_matrices(o, Ng, past, cur, des, "update", k);
-            compare_phases(o, a, past, cur, des, k);
-          }
-          if (fails) break;
-        }
-        planner_oracle_destroy(o);
-        ran++;
-        if (fails) { fprintf(stderr, "stopped at N_gait %d rows %d n_steps %d k_mpc %d\n", Ng, rows, a.n_steps, K); return 1; }
-      }
+      for (int g = 0; g < 8; g++)
+        if (!one_configuration(Ng, rows, Args{rows * dt, dt, grid[g][0], grid[g][1]}, 0.002)) return 1;
     }
-  printf("primitive checks %ld, configurations run %ld, refused %ld, gait updates %ld\n", nprim, ran, refused, updates);
+  const long ran02 = ran, refused02 = refused;
+  // off the 0.02 s step, where T_gait and dt_mpc are rounded decimals and their quotient can miss its integer: the (T_gait, dt_mpc)
+  // pairs of tests/planner_cases.py STEPS as written there, in tables from too small to the widest, and every period of 1 .. 24 rows at
+  // the five steps with T_gait = rows * dt_mpc as a caller would compute it
+  static const struct { double T_gait, dt_mpc; int rows, n_steps, k_mpc; } steps[5] = {
+      {0.20, 0.010, 20, 16, 5}, {0.48, 0.040, 12, 8, 20}, {0.32, 0.016, 20, 20, 8}, {0.36, 0.024, 15, 12, 12}, {0.40, 0.025, 16, 12, 5}};
+  for (auto& s : steps) {
+    static const int tables[] = {9, 12, 13, 15, 16, 17, 20, 21, 24, 40, 63};
+    for (int Ng : tables)
+      for (int form = 0; form < 2; form++)
+        if (!one_configuration(Ng, s.rows, Args{s.T_gait, s.dt_mpc, form ? 1 : s.n_steps, form ? 3 : s.k_mpc}, s.dt_mpc / s.k_mpc)) return 1;
+    for (int rows = 1; rows <= 24; rows++)
+      for (int Ng = (rows > 3 ? rows - 2 : 2); Ng <= rows + 4; Ng += 2)
+        if (!one_configuration(Ng, rows, Args{rows * s.dt_mpc, s.dt_mpc, rows < 9 ? rows : 8, 4}, s.dt_mpc / 4)) return 1;
+  }
+  printf("primitive checks %ld, configurations run %ld, refused %ld, gait updates %ld, off the 0.02 s step run %ld, refused %ld\n", nprim, ran02, refused02,
+         updates, ran - ran02, refused - refused02);
   return fails ? 1 : 0;
 }
 """
@@ -241,7 +264,11 @@ def test_gait_masks_against_the_dense_oracle_under_the_sanitizers(tmp_path):
     Part B: every N_gait in 2..63 x every period of 1..N_gait rows x n_steps in {1, 4, 16, 32} x k_mpc in {1, 4}.  Where the size rule refuses, the oracle refuses too; where it accepts, no generator writes at or above row N_gait,
     and a schedule of codes (consecutive, during a transition, static and away again, on a non-rolling iteration) runs to two
     of the longest periods past the last code with the three matrices, newPhase, and phase_duration + remainingTime (row 0, row
-    1, the last live row and two random live rows, four feet, both values) equal to the dense oracle's after every update."""
+    1, the last live row and two random live rows, four feet, both values) equal to the dense oracle's after every update.
+    Part C: the same off the 0.02 s MPC step -- the five (T_gait, dt_mpc) pairs of planner_cases.STEPS in eleven table sizes, and
+    every period of 1..24 rows at dt_mpc 0.01, 0.04, 0.016, 0.024 and 0.025 with T_gait = rows * dt_mpc: neither is a binary
+    fraction, the quotient T_gait / dt_mpc misses its integer by an ulp in a tenth of these pairs, and lround(0.5 T_gait / dt_mpc),
+    phase_duration = cnt * dt_mpc and the size rule have to round as the dense oracle does."""
     if shutil.which("g++") is None or shutil.which("gcc") is None:
         pytest.skip("g++ / gcc not available")
     src, obj, exe = tmp_path / "gait_host.cpp", tmp_path / "planner_oracle.o", tmp_path / "gait_host"
@@ -256,10 +283,13 @@ def test_gait_masks_against_the_dense_oracle_under_the_sanitizers(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
     print(r.stdout.strip())
     assert r.returncode == 0 and r.stderr.strip() == "", (r.returncode, r.stderr[-3000:])
-    m = re.fullmatch(r"primitive checks (\d+), configurations run (\d+), refused (\d+), gait updates (\d+)", r.stdout.strip())
+    m = re.fullmatch(r"primitive checks (\d+), configurations run (\d+), refused (\d+), gait updates (\d+), off the 0.02 s step run (\d+), refused (\d+)",
+                     r.stdout.strip())
     assert m, r.stdout[-500:]
-    nprim, ran, refused, updates = (int(x) for x in m.groups())
+    nprim, ran, refused, updates, ran_steps, refused_steps = (int(x) for x in m.groups())
     assert ran + refused == 8 * sum(range(2, 64)) and ran > 10000 and refused > 1000 and nprim > 500000, r.stdout
+    assert ran_steps + refused_steps == 5 * (11 * 2 + sum(len(range(max(rows - 2, 2), rows + 5, 2)) for rows in range(1, 25))), r.stdout
+    assert ran_steps > 250 and refused_steps > 100, r.stdout
 
 
 # the probes that used to end in glibc aborts ("corrupted size vs. prev_size") or in silent writes beyond the matrices

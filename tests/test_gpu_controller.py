@@ -79,6 +79,12 @@ def test_glue_stages_match_oracle():
 DEFAULT_CFG = dict(dt_wbc=0.002, dt_mpc=0.02, k_mpc=10, T_gait=0.32, T_mpc=0.32, N_gait=20, h_ref=0.2229)
 # other timings than the reference's yaml: 1 kHz WBC, MPC every 20th iteration, a 0.40 s gait on a 0.24 s horizon
 ALT_CFG = dict(dt_wbc=0.001, dt_mpc=0.02, k_mpc=20, T_gait=0.40, T_mpc=0.24, N_gait=26, h_ref=0.21)
+# off the 0.02 s MPC step (dt_wbc * k_mpc = dt_mpc): a 16-step horizon of 0.16 s on a 32-row gait, 0.04 s steps, and 0.016 s steps
+# whose period is the horizon (20 rows)
+STEP10 = dict(dt_wbc=0.002, dt_mpc=0.010, k_mpc=5, T_gait=0.32, T_mpc=0.16, N_gait=36, h_ref=0.2229)
+STEP40 = dict(dt_wbc=0.002, dt_mpc=0.040, k_mpc=20, T_gait=0.48, T_mpc=0.32, N_gait=20, h_ref=0.2229)
+STEP16 = dict(dt_wbc=0.002, dt_mpc=0.016, k_mpc=8, T_gait=0.32, T_mpc=0.32, N_gait=24, h_ref=0.2229)
+STEP_CFGS = {"STEP10": (STEP10, 16, 45), "STEP40": (STEP40, 8, 85), "STEP16": (STEP16, 20, 37)}  # (configuration, n_steps, iterations)
 
 
 def test_closed_loop_other_timings(oracle_mod):
@@ -89,6 +95,19 @@ def test_closed_loop_three_gait_periods(oracle_mod):
     """480 iterations (three gait periods, 48 MPC solves per robot): the footstep table has rolled through every phase three times
     and every foot has flown three times when the comparison with the chained oracles ends."""
     _closed_loop(oracle_mod, "sync", True, DEFAULT_CFG, 480, B=4)
+
+
+@pytest.mark.parametrize("name,mode", [("STEP10", "sync"), ("STEP40", "sync"), ("STEP16", "sync"), ("STEP10", "async_lag3")])
+def test_closed_loop_at_other_mpc_steps(oracle_mod, name, mode):
+    """The whole chain (planners, MPC, glue, WBC, result) against the chained oracles with dt_mpc 0.010, 0.040 and 0.016 s: at least
+    five MPC solves per robot, B = 5, the tolerances of _closed_loop.  The asynchronous run of STEP10 adopts every result three
+    iterations late, so the shift of the stored result (qrw_mpc_result_shift) runs at a step other than 0.02 s too.
+    Worst relative deviation as printed on the device:
+        STEP10 1.7e-12   STEP40 4.3e-11   STEP16 1.6e-12   STEP10 with a lag of three 1.7e-12"""
+    cfg, n_steps, iters = STEP_CFGS[name]
+    assert int(round(cfg["T_mpc"] / cfg["dt_mpc"])) == n_steps and cfg["k_mpc"] * cfg["dt_wbc"] == pytest.approx(cfg["dt_mpc"], rel=1e-15)
+    assert iters > 4 * cfg["k_mpc"]
+    _closed_loop(oracle_mod, mode, True, cfg, iters)
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "separate"])
@@ -606,7 +625,7 @@ def test_staggered_stream_groups_equal_single_handles_started_late(free, default
         assert torch.equal(flags[sl], one.error_flag)
 
 
-@pytest.mark.parametrize("cfg", ["default", "alt", "short_period", "full20", "wide"])
+@pytest.mark.parametrize("cfg", ["default", "alt", "short_period", "full20", "wide", "step10", "step24", "step10_rowwise"])
 def test_control_pre_quad_form_equals_the_thread_form_through_gait_changes(cfg, monkeypatch):
     """qrw_control_pre's quad kernel (one quad per robot: touch-downs of the footstep table computed wave-together, mask arithmetic
     for getPhaseDuration) against the one-thread-per-robot form (QRW_PRE_QUAD=0, the kernel the planner parity tests compare with
@@ -620,10 +639,16 @@ def test_control_pre_quad_form_equals_the_thread_form_through_gait_changes(cfg, 
         B, N, kw, k_mpc = 21, 16, dict(), 10
     elif cfg == "alt":  # 0.40 s gait on a 0.24 s horizon, 26 gait rows, 1 kHz loop
         B, N, kw, k_mpc = 21, 12, dict(N_gait=26, T_gait=0.40, dt_wbc=0.001), 20
-    elif cfg == "short_period":  # a 0.08 s gait period in 24 rows: up to six touch-downs per foot in the table (the quad form's row-wise fallback)
+    elif cfg == "short_period":  # a 0.08 s gait period in 24 rows (a 4-step horizon: two touch-downs per foot; the row-wise form is step10_rowwise's)
         B, N, kw, k_mpc = 21, 4, dict(N_gait=24, T_gait=0.08), 10
     elif cfg == "full20":  # a 0.40 s period in 20 rows: the period fills the gait table (tests/planner_cases.py)
         B, N, kw, k_mpc = 21, 16, dict(N_gait=20, T_gait=0.40), 10
+    elif cfg == "step10":  # a 0.01 s MPC step: 20 rows per period in 24 (tests/planner_cases.py STEPS)
+        B, N, kw, k_mpc = 21, 16, dict(N_gait=24, T_gait=0.20, dt_mpc=0.01), 5
+    elif cfg == "step24":  # a 0.024 s MPC step: 15 rows per period, trot and walk write 16
+        B, N, kw, k_mpc = 21, 12, dict(N_gait=20, T_gait=0.36, dt_mpc=0.024), 12
+    elif cfg == "step10_rowwise":  # 0.01 s steps, a 4-row period under a 20-step horizon: five touch-downs per foot in the table, more
+        B, N, kw, k_mpc = 21, 20, dict(N_gait=24, T_gait=0.04, dt_mpc=0.01), 5  # than the quad form computes wave-together (its row-wise form)
     else:  # "wide": 63 rows, a 1.22 s period (61 rows, a 62-row trot: masks up to bit 61), a 32-step horizon, k_mpc 4
         B, N, kw, k_mpc = 21, 32, dict(N_gait=63, T_gait=1.22, dt_wbc=0.005), 4
     Ng = kw.get("N_gait", 20)
@@ -641,7 +666,7 @@ def test_control_pre_quad_form_equals_the_thread_form_through_gait_changes(cfg, 
     outs = [None, None]
     keys = ("q", "v", "h_v", "v_ref", "oRh_oTh", "xref", "fsteps", "gait", "target", "feet_pva", "contacts", "x_f_wbc", "q_wbc", "b_v",
             "f_cmd", "feet_cmd")
-    worst = 0.0
+    worst, most_td = 0.0, 0
     for k in range(450):
         vf = np.zeros((B, 18))
         vf[:, :6] = vref + rng.uniform(-0.05, 0.05, (B, 6))
@@ -659,6 +684,9 @@ def test_control_pre_quad_form_equals_the_thread_form_through_gait_changes(cfg, 
             outs[e] = eng.control_pre(k, _t(vref), _t(qf), _t(vf), _t(rpy), c, x_f_mpc=(None if solve else _t(x_f)), out=outs[e],
                                       mpc_inputs=solve)
         torch.cuda.synchronize()
+        if solve:  # touch-downs (swing -> stance) per foot in the table: above four the quad form walks the rows instead
+            g = outs[1]["gait"].cpu().numpy()
+            most_td = max(most_td, int(((g[:, 1:] == 1) & (g[:, :-1] == 0)).sum(1).max()))
         for key in keys:
             if not solve and key in ("fsteps", "gait"):
                 continue
@@ -684,6 +712,8 @@ def test_control_pre_quad_form_equals_the_thread_form_through_gait_changes(cfg, 
                 rows = Ng if solve else 2  # (rows >= 2 of the quad form's table wait for the next solving iteration)
                 assert np.allclose(ta[:rows], tb[:rows], rtol=1e-11, atol=1e-13), (k, b)
     assert worst < 1e-9
+    print("%s: at most %d touch-downs per foot in a table" % (cfg, most_td))
+    assert (most_td > 4) == (cfg == "step10_rowwise"), most_td
 
 
 @pytest.mark.parametrize("mode", ["sync", "async_lag3"])

@@ -12,13 +12,20 @@ def rel_err(a, ref):
     return np.abs(a - ref).max() / max(np.abs(ref).max(), 1e-12)
 
 
-def run_sequence(oracle_mod, synth_mod, B, N, gaits, steps, seed0, closed_loop=True, N_gait=None):
+def run_sequence(oracle_mod, synth_mod, B, N, gaits, steps, seed0, closed_loop=True, N_gait=None, dt=0.02, guard=False, seen=None):
+    """dt: the MPC step of the inputs, the handle and the oracle (T_gait = dt * N).  guard: the oracle's second build
+    (-O3 -march=native) runs beside the strict one and must take its iteration count and status on every instance of every call,
+    which is what makes the same demand on the device a matter of the code and not of rounding.  seen: a set the oracle's
+    statuses are added to."""
     import qrw_hip
 
     N_gait = N_gait or max(20, N + 4)
-    sb = synth_mod.SyntheticBatch(B, N, N_gait=N_gait, gaits=gaits, seed0=seed0)
-    eng = qrw_hip.Batch(B, n_steps=N, N_gait=N_gait, T_gait=0.02 * N)
-    refs = [oracle_mod.MPC(0.02, N, 0.02 * N, N_gait) for _ in range(B)]
+    sb = synth_mod.SyntheticBatch(B, N, N_gait=N_gait, dt=dt, gaits=gaits, seed0=seed0)
+    eng = qrw_hip.Batch(B, n_steps=N, N_gait=N_gait, dt_mpc=dt, T_gait=dt * N)
+    refs = [oracle_mod.MPC(dt, N, dt * N, N_gait) for _ in range(B)]
+    if guard:
+        oracle_mod.build(fast=True)
+    fast = [oracle_mod.MPC(dt, N, dt * N, N_gait, fast=True) for _ in range(B)] if guard else []
     x0 = None
     worst = 0.0
     for s in range(steps):
@@ -29,6 +36,11 @@ def run_sequence(oracle_mod, synth_mod, B, N, gaits, steps, seed0, closed_loop=T
         for b in range(B):
             assert refs[b].run(s, d["xref"][b], d["fsteps"][b]) == 0
             ref[b] = refs[b].get_latest_result()
+            if guard:
+                assert fast[b].run(s, d["xref"][b], d["fsteps"][b]) == 0
+                assert (fast[b].iter, fast[b].status) == (refs[b].iter, refs[b].status), ("the oracle's two builds", s, b)
+            if seen is not None:
+                seen.add(int(refs[b].status))
             assert st["iters"][b] == refs[b].iter, (s, b, st["iters"][b], refs[b].iter)
             assert st["status"][b] == refs[b].status
             assert np.isclose(st["rho"][b], refs[b].rho, rtol=1e-9)

@@ -60,6 +60,37 @@ def test_wbc_sequence_matches_oracle(oracle_mod, synth_mod, lanes):
             assert np.array_equal(st["k_since_contact"][b], r.k_since_contact.ravel())
 
 
+@LANES
+def test_wbc_step_does_not_depend_on_dt_wbc(synth_mod, lanes):
+    """Two handles with dt_wbc 0.002 and 0.005 given the eight calls of test_wbc_sequence_matches_oracle: every output, the
+    iteration counts and k_since_contact are equal bit for bit.  The reference's whole-body step does not use its time step:
+    src/InvKin.cpp:6 stores dt and nothing ever reads it (the oracle built either way gives identical outputs for 0.001, 0.002,
+    0.0025 and 0.005 on these inputs), so a handle's dt_wbc must reach the planners and the glue only."""
+    import qrw_hip
+
+    B = 21
+    sb = synth_mod.SyntheticBatch(B, 16, gaits=("trot", "walk", "static"), seed0=91000)
+    engs = [qrw_hip.Batch(B, dt_wbc=dt) for dt in (0.002, 0.005)]
+    for eng in engs:
+        eng.wbc_set_lanes(lanes)
+    rng = np.random.default_rng(0)
+    for s in range(8):
+        d = sb.step(s)
+        quat = rng.normal(size=(B, 4))
+        d["q"][:, 3:7] = quat / np.linalg.norm(quat, axis=1, keepdims=True) if s >= 4 else d["q"][:, 3:7]
+        d["q"][:, :3] += rng.uniform(-0.2, 0.2, (B, 3)) if s >= 4 else 0
+        d["dq"][:, 3:6] = rng.uniform(-0.5, 0.5, (B, 3))
+        f = f_cmd_for(d["contacts"], rng)
+        o = [eng.wbc_compute_host(d["q"], d["dq"], f, d["contacts"], d["pgoals"], d["vgoals"], d["agoals"]) for eng in engs]
+        st = [eng.wbc_stats() for eng in engs]
+        assert sorted(o[0]) == sorted(o[1]) and {"tau_ff", "qdes", "vdes", "f_with_delta", "ddq_res", "feet"} <= set(o[0])
+        for key in o[0]:
+            assert np.array_equal(o[0][key], o[1][key]), (s, key)
+        for key in ("iters", "status", "k_since_contact"):
+            assert np.array_equal(st[0][key], st[1][key]), (s, key)
+        assert (st[0]["status"] == 1).all() and np.isfinite(o[0]["tau_ff"]).all()
+
+
 def test_standalone_pieces_match_oracle(oracle_mod, synth_mod):
     import qrw_hip
 

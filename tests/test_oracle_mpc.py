@@ -19,12 +19,12 @@ def skew(v):
     return np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
 
 
-def dense_qp(xref, fsteps, N, first_call=False):
-    """Independent dense assembly of (A, l, u, Pdiag) per SURVEY.md Appendix A.1."""
+def dense_qp(xref, fsteps, N, first_call=False, dt=DT):
+    """Independent dense assembly of (A, l, u, Pdiag) per SURVEY.md Appendix A.1, at the MPC step dt."""
     n, m = 24 * N, 44 * N
     A = np.zeros((m, n))
     Ad = np.eye(12)
-    Ad[:6, 6:] = DT * np.eye(6)
+    Ad[:6, 6:] = dt * np.eye(6)
     gait = (fsteps[:, 0::3] != 0).astype(float)
     u = np.zeros(m)
     l = np.zeros(m)
@@ -34,7 +34,7 @@ def dense_qp(xref, fsteps, N, first_call=False):
             A[12 * k:12 * k + 12, 12 * (k - 1):12 * k] = Ad
         B = np.zeros((12, 12))
         for i in range(4):
-            B[6:9, 3 * i:3 * i + 3] = DT / MASS * np.eye(3)
+            B[6:9, 3 * i:3 * i + 3] = dt / MASS * np.eye(3)
         c, s = np.cos(xref[5, k]), np.sin(xref[5, k])
         R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
         Iinv = np.linalg.inv(R.T @ GI @ R)
@@ -44,7 +44,7 @@ def dense_qp(xref, fsteps, N, first_call=False):
                 lever = foot - xref[0:3, k]
             else:
                 lever = fsteps[k, 3 * i:3 * i + 3] - (xref[0:3, k] + np.array([0, 0, -0.03]))
-            B[9:12, 3 * i:3 * i + 3] = DT * (Iinv @ skew(lever))
+            B[9:12, 3 * i:3 * i + 3] = dt * (Iinv @ skew(lever))
         A[12 * k:12 * k + 12, 12 * (N + k):12 * (N + k) + 12] = B
         for i in range(4):
             for cc in range(3):
@@ -59,7 +59,7 @@ def dense_qp(xref, fsteps, N, first_call=False):
             l[r0:r0 + 4] = -np.inf
             l[r0 + 4] = -25.0
         rhs = np.zeros(12)
-        rhs[8] = np.float64(np.float32(9.81)) * DT
+        rhs[8] = np.float64(np.float32(9.81)) * dt
         rhs += xref[:, k + 1] - Ad @ xref[:, k]
         u[12 * k:12 * k + 12] = rhs
         l[12 * k:12 * k + 12] = rhs
@@ -75,12 +75,13 @@ def csc_to_dense(p, i, x, m, n):
     return A
 
 
-@pytest.mark.parametrize("N", [16, 32])
-def test_qp_assembly_matches_independent_dense_build(oracle_mod, synth_mod, N):
-    sb = synth_mod.SyntheticBatch(2, N, gaits=("trot", "walk"), seed0=99)
-    mpc = [oracle_mod.MPC(DT, N, DT * N, 40 if N > 20 else 20) for _ in range(2)]
-    sb.N_gait = mpc[0].N_gait
-    sb = synth_mod.SyntheticBatch(2, N, N_gait=mpc[0].N_gait, gaits=("trot", "walk"), seed0=99)
+@pytest.mark.parametrize("dt,N,N_gait", [(0.02, 16, 20), (0.02, 32, 40), (0.01, 16, 20), (0.04, 8, 20), (0.016, 20, 24), (0.025, 12, 20)])
+def test_qp_assembly_matches_independent_dense_build(oracle_mod, synth_mod, dt, N, N_gait):
+    """The oracle's CSC matrices, bounds and cost against dense_qp over three calls (the first included), at the reference's
+    0.02 s step and at four others: the GPU tests of tests/test_gpu_mpc_steps.py compare the device with the oracle at these
+    steps, and this is what holds the oracle there."""
+    mpc = [oracle_mod.MPC(dt, N, dt * N, N_gait) for _ in range(2)]
+    sb = synth_mod.SyntheticBatch(2, N, N_gait=N_gait, dt=dt, gaits=("trot", "walk"), seed0=99)
     for s in range(3):
         d = sb.step(s)
         for b in range(2):
@@ -88,7 +89,7 @@ def test_qp_assembly_matches_independent_dense_build(oracle_mod, synth_mod, N):
             (p, i, x), (pp, pi, px), lo, up = mpc[b].qp()
             assert p[-1] == 126 * N - 18  # nnz invariant [SURVEY §8(c)(2)]
             A = csc_to_dense(p, i, x, 44 * N, 24 * N)
-            A_ref, l_ref, u_ref, Pd = dense_qp(d["xref"][b], d["fsteps"][b], N, first_call=(s == 0))
+            A_ref, l_ref, u_ref, Pd = dense_qp(d["xref"][b], d["fsteps"][b], N, first_call=(s == 0), dt=dt)
             assert np.allclose(A, A_ref, rtol=1e-12, atol=1e-15), (s, b)
             assert np.allclose(up, u_ref, rtol=1e-12, atol=1e-14)
             assert np.array_equal(np.isinf(lo), np.isinf(l_ref))

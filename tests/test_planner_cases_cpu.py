@@ -42,7 +42,8 @@ def test_each_parameter_alone_moves_the_oracle_by_more_than_1000_bounds(oracle_m
 
 
 def test_cases_are_what_their_names_say(oracle_mod):
-    want = dict(full20=(20, 20), walk_fills=(18, 20), odd=(15, 16), wide=(61, 62), tight=(8, 8))
+    want = dict(full20=(20, 20), walk_fills=(18, 20), odd=(15, 16), wide=(61, 62), tight=(8, 8),
+                step10=(20, 20), step40=(12, 12), step16=(20, 20), step24=(15, 16), step25=(16, 16))
     for case, (rows, need) in want.items():
         c = pc.CASES[case]
         assert pc.lround(c["T_gait"] / c["dt_mpc"]) == rows and pc.rows_needed(case) == need
@@ -55,6 +56,10 @@ def test_cases_are_what_their_names_say(oracle_mod):
         assert K - 1 - max(events) >= 2 * need * c["k_mpc"]                               # two of the longest periods after the last change
         assert any(k % c["k_mpc"] for k in events) and any(k % c["k_mpc"] == 0 for k in events)
     assert pc.CASES["tight"]["N"] + 1 == pc.CASES["tight"]["N_gait"] and pc.CASES["wide"]["N_gait"] == 63
+    assert set(want) == set(pc.LIMITS + pc.STEPS)
+    for case in pc.STEPS:  # off the 0.02 s step, with the loop's step a whole fraction of the MPC's
+        c = pc.CASES[case]
+        assert c["dt_mpc"] != 0.02 and c["k_mpc"] * c["dt_wbc"] == pytest.approx(c["dt_mpc"], rel=1e-15) and c["seq"] == "limits"
     for case in pc.CASES:
         seq = pc.sequence(case)
         assert (seq["vref"][:, 0, 5] == 0.0).any() and (seq["code"] != 0).any() and np.abs(seq["hv"] - seq["vref"]).max() > 0.05

@@ -8,7 +8,7 @@ import pytest
 import planner_cases as pc
 import planner_numpy as pn
 
-CONFIGS = ("default", "alt", "short_period", "full20", "wide", "TUNED", "wild")
+CONFIGS = ("default", "alt", "short_period", "full20", "wide", "TUNED", "wild") + pc.STEPS
 ROBOTS = 3  # of the case's robots (the oracle's run over all of them is shared with the other tests)
 
 
@@ -60,6 +60,16 @@ def test_rule_and_refusals_agree_with_the_oracle(oracle_mod):
         for n_steps in (1, 8, 16, 32):
             for T in (0.16, 0.30, 0.32, 0.36, 0.40, 1.22, 1.24, 1.26):
                 assert pn.table_fits(N_gait, n_steps, T, 0.02) == bool(lib.planner_oracle_table_fits(N_gait, n_steps, T, 0.02)), (N_gait, n_steps, T)
+    # off the 0.02 s step: periods of 1 .. 64 rows (T = rows * dt as the caller would compute it) and periods with halves in them
+    yes = no = 0
+    for dt in (0.01, 0.016, 0.024, 0.025, 0.04):
+        for N_gait in (2, 9, 15, 16, 18, 20, 24, 63, 64):
+            for n_steps in (1, 8, 12, 16, 20, 32):
+                for T in [rows * dt for rows in (1, 2, 7, 8, 12, 15, 16, 18, 19, 20, 21, 24, 61, 62, 63, 64)] + [7.5 * dt, 12.5 * dt, 0.20, 0.32, 0.36, 0.40, 0.48]:
+                    fits = pn.table_fits(N_gait, n_steps, T, dt)
+                    assert fits == bool(lib.planner_oracle_table_fits(N_gait, n_steps, T, dt)), (N_gait, n_steps, T, dt)
+                    yes, no = yes + fits, no + (not fits)
+    assert yes > 500 and no > 500, (yes, no)
     with pytest.raises(ValueError):
         pn.Planner(N_gait=63, T_gait=1.24)
     with pytest.raises(ValueError):
