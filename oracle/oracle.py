@@ -94,6 +94,7 @@ def load(fast=False):
         "wbc_oracle_qp_rho": (C.c_double, [vp]),
         "wbc_oracle_get_feet": (None, [vp, _dp, _dp, _dp]),
         "wbc_oracle_get_k_since_contact": (None, [vp, _dp]),
+        "wbc_oracle_get_ddq_res": (None, [vp, _dp]),
         "planner_oracle_create": (vp, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, _dp,
                                        C.c_double, C.c_double, _dp, _dp]),
         "planner_oracle_destroy": (None, [vp]),
@@ -411,6 +412,20 @@ class WbcBatch:
         st = np.array([self._lib.wbc_oracle_qp_status(h) for h in self._hs], dtype=np.int32)
         rho = np.array([self._lib.wbc_oracle_qp_rho(h) for h in self._hs])
         return it, st, rho
+
+    def ddq_res(self):
+        """(B, 6): ddq_res of the last compute (the batch call does not return it)."""
+        out = np.zeros((self.B, 6))
+        for b, h in enumerate(self._hs):
+            self._lib.wbc_oracle_get_ddq_res(h, _ptr(out[b]))
+        return out
+
+    def feet(self):
+        """(B, 3, 3, 4): feet_pos, feet_err, feet_vel of the last compute."""
+        out = np.zeros((self.B, 3, 3, 4))
+        for b, h in enumerate(self._hs):
+            self._lib.wbc_oracle_get_feet(h, _ptr(out[b, 0]), _ptr(out[b, 1]), _ptr(out[b, 2]))
+        return out
 
     def compute(self, q, dq, f_cmd, contacts, pgoals, vgoals, agoals, threads):
         B = self.B

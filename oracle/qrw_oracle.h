@@ -106,6 +106,7 @@ int wbc_oracle_qp_status(const wbc_oracle *o); /* tests only */
 double wbc_oracle_qp_rho(const wbc_oracle *o);  /* tests only */
 void wbc_oracle_get_feet(const wbc_oracle *o, double *feet_pos3x4, double *feet_err3x4, double *feet_vel3x4);
 void wbc_oracle_get_k_since_contact(const wbc_oracle *o, double *k4);
+void wbc_oracle_get_ddq_res(const wbc_oracle *o, double *ddq6); /* of the last compute (tests only) */
 
 /* --------- planners feeding the hot path (oracle/planner_oracle.c) --------- */
 typedef struct planner_oracle planner_oracle;

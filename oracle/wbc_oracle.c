@@ -377,6 +377,7 @@ void wbc_oracle_get_feet(const wbc_oracle *o, double *p, double *e, double *v) {
 void wbc_oracle_get_k_since_contact(const wbc_oracle *o, double *k4) {
   memcpy(k4, o->k_since_contact, sizeof(o->k_since_contact));
 }
+void wbc_oracle_get_ddq_res(const wbc_oracle *o, double *ddq6) { qpwbc_oracle_get_ddq_res(o->box_qp, ddq6); }
 
 int wbc_oracle_compute_batch(wbc_oracle **o, int B, const double *q, const double *dq, const double *f_cmd,
                              const double *contacts, const double *pgoals, const double *vgoals, const double *agoals,

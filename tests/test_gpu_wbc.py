@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+import wbc_recompose as wr
+
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
 
@@ -10,15 +12,19 @@ def rel_err(a, ref):
     return np.abs(a - ref).max() / max(np.abs(ref).max(), 1e-12)
 
 
-def f_cmd_for(contacts, rng=None):
-    B = contacts.shape[0]
-    f = np.zeros((B, 12))
-    f[:, 2::3] = contacts * 24.5 / np.maximum(contacts.sum(1, keepdims=True), 1)
-    f[:, 0::3] = contacts * 0.7
-    f[:, 1::3] = contacts * -0.4
-    if rng is not None:
-        f += np.repeat(contacts, 3, axis=1) * rng.normal(size=(B, 12))
-    return f
+f_cmd_for = wr.f_cmd_for
+
+
+def _report(what, lanes, big, dist):
+    """The measured figures of a recomposition check: the worst residual per output (absolute, and in bounds of the family) and
+    the kernel's and the strict oracle's largest distance to the QP's optimum."""
+    print("%s, lanes %s: worst residual %s; distance to the optimum: kernel %.2e N, strict oracle %.2e N (ratio %.2f), worst bound "
+          "violation %.2e N" % (what, lanes, "  ".join("%s %.2e (%.3f of its bound)" % (k, big[k], big[k] / wr.bound(what, k)) for k in wr.OUTPUTS),
+                                dist[0], dist[1], dist[0] / dist[1], dist[2]))
+
+
+def _worse(big, new):
+    return {k: max(big.get(k, 0.0), new[k]) for k in new}
 
 
 # Both shipped forms of the full WBC step stand directly under the oracle: wbc16_kernel (16 lanes per robot, the default) and
@@ -29,35 +35,32 @@ LANES = pytest.mark.parametrize("lanes", [16, 4], ids=["wbc16_kernel", "wbc_kern
 
 @LANES
 def test_wbc_sequence_matches_oracle(oracle_mod, synth_mod, lanes):
+    """Eight warm-started calls at B = 21 (wbc_recompose.family("sequence")) against the oracle as before (iteration counts,
+    1e-4 relative per output, feet, k_since_contact), and split at the QP (tests/wbc_recompose.py): qdes, vdes, feet, ddq_res and
+    tau_ff of EVERY robot within 100 x the oracle's one-ulp spread of what the oracle's pieces give for the kernel's own f (absolute,
+    per output), and f within 2 x the oracle's largest distance to the QP's optimum over the run."""
     import qrw_hip
 
-    B = 21  # not a multiple of 16: exercises the padded quads of the last wavefront
-    sb = synth_mod.SyntheticBatch(B, 16, gaits=("trot", "walk", "static"), seed0=91000)
+    calls, ref = wr.family("sequence", synth_mod), wr.oracle_run(oracle_mod, synth_mod, "sequence")
+    ref_w, _ = wr.oracle_analysis(oracle_mod, synth_mod, "sequence")
+    B = len(calls[0]["q"])
+    assert B == 21  # not a multiple of 16: exercises the padded quads of the last wavefront
     eng = qrw_hip.Batch(B)
     eng.wbc_set_lanes(lanes)
-    refs = [oracle_mod.WbcController(0.002) for _ in range(B)]
-    rng = np.random.default_rng(0)
-    for s in range(8):
-        d = sb.step(s)
-        # random base pose / twist: the reference always passes the identity pose, the kernel must not assume it
-        quat = rng.normal(size=(B, 4))
-        d["q"][:, 3:7] = quat / np.linalg.norm(quat, axis=1, keepdims=True) if s >= 4 else d["q"][:, 3:7]
-        d["q"][:, :3] += rng.uniform(-0.2, 0.2, (B, 3)) if s >= 4 else 0
-        d["dq"][:, 3:6] = rng.uniform(-0.5, 0.5, (B, 3))
-        f = f_cmd_for(d["contacts"], rng)
+    big, got_w = {}, []
+    for s, (d, r) in enumerate(zip(calls, ref)):
+        f = d["f_cmd"]
         o = eng.wbc_compute_host(d["q"], d["dq"], f, d["contacts"], d["pgoals"], d["vgoals"], d["agoals"])
         st = eng.wbc_stats()
         for b in range(B):
-            r = refs[b]
-            r.compute(d["q"][b], d["dq"][b], f[b], d["contacts"][b], d["pgoals"][b], d["vgoals"][b], d["agoals"][b])
-            assert st["iters"][b] == r.qp_iter and st["status"][b] == 1
-            for key, ref in (("tau_ff", r.tau_ff), ("qdes", r.qdes), ("vdes", r.vdes[:, 0]),
-                             ("f_with_delta", r.f_with_delta[:, 0]), ("ddq_res", r.ddq_res)):
-                assert rel_err(o[key][b], ref) < RTOL, (s, b, key)
-            p, e, v = r.feet()
-            assert np.allclose(o["feet"][b, 0], p, atol=1e-12) and np.allclose(o["feet"][b, 1], e, atol=1e-12)
-            assert np.allclose(o["feet"][b, 2], v, atol=1e-12)
-            assert np.array_equal(st["k_since_contact"][b], r.k_since_contact.ravel())
+            assert st["iters"][b] == r["iters"][b] and st["status"][b] == 1
+            for key in ("tau_ff", "qdes", "vdes", "f_with_delta", "ddq_res"):
+                assert rel_err(o[key][b], r[key][b]) < RTOL, (s, b, key)
+            assert np.allclose(o["feet"][b], r["feet"][b], atol=1e-12)
+            assert np.array_equal(st["k_since_contact"][b], r["k_since_contact"][b])
+        got_w.append(wr.batch_worst(oracle_mod, d, o, xstar=ref_w[s]["xstar"]))
+        big = _worse(big, wr.check("sequence", got_w[-1], (s, lanes)))
+    _report("sequence", lanes, big, wr.check_optimum(got_w, ref_w, (lanes,)))
 
 
 @LANES
@@ -137,6 +140,7 @@ def test_dropin_classes_match_oracle(oracle_mod, synth_mod):
     ref_mpc = oracle_mod.MPC(0.02, N, 0.32, 20)
     ref_wbc = oracle_mod.WbcController(0.002)
     x0 = None
+    big, dists = {}, []
     for s in range(5):
         d = sb.step(s, x0)
         k = 10 * s
@@ -156,6 +160,17 @@ def test_dropin_classes_match_oracle(oracle_mod, synth_mod):
         assert rel_err(wbc.vdes, ref_wbc.vdes) < RTOL and rel_err(wbc.f_with_delta, ref_wbc.f_with_delta) < RTOL
         assert np.array_equal(wbc.k_since_contact, ref_wbc.k_since_contact)
         assert np.allclose(wbc.invKin.cpp_posf, oracle_mod.fixed_feet(d["q"][0][7:], d["dq"][0][6:])[0], atol=1e-12)
+        # split at the QP (tests/wbc_recompose.py), with the forces this class was given (the device's MPC result)
+        inp = wr.robot(dict(d, f_cmd=x_f[12:, 0][None]), 0)
+        cand = dict(tau_ff=wbc.tau_ff, qdes=wbc.qdes, vdes=wbc.vdes[:, 0], f_with_delta=wbc.f_with_delta[:, 0], ddq_res=wbc.ddq_res,
+                    feet=np.stack([wbc.feet_pos, wbc.feet_err, wbc.feet_vel]))
+        res = wr.recompose(oracle_mod, inp, cand)
+        big = _worse(big, wr.check("dropin", wr.worst(res), (s,)))
+        own = wr.recompose(oracle_mod, inp, wr.oracle_candidate(ref_wbc), xstar=res["xstar"])  # (f_cmd differs at 1e-7: same optimum to that)
+        dists.append((res["opt_dist"], own["opt_dist"], res["bound_viol"], res["solved"]))
+    dists = np.array(dists)
+    assert dists[:, 3].all() and (dists[:, 0] <= 2.0 * dists[:, 1].max()).all() and (dists[:, 2] <= 2.0 * dists[:, 1].max()).all(), dists
+    _report("dropin", "16 (wbc_controller)", big, (dists[:, 0].max(), dists[:, 1].max(), dists[:, 2].max()))
     assert wrap.stop_parallel_loop() == 0
     # bound-class surface (python/gepadd.cpp): QPWBC / InvKin / MPC getters
     d = sb.step(0)
@@ -206,28 +221,28 @@ def test_async_wrapper_returns_previous_then_new_result(synth_mod):
 @LANES
 def test_contact_patterns_from_flight_to_full_stance(oracle_mod, synth_mod, lanes):
     """Every one of the 16 contact sets (flight phase, single support, ..., four feet), changing from call to call on
-    the same solver instance (the QP's matrix changes, the warm start is kept): GPU vs oracle."""
+    the same solver instance (the QP's matrix changes, the warm start is kept): GPU vs oracle, and split at the QP as in
+    test_wbc_sequence_matches_oracle (flight and single support included: with no stance foot ddq_res* = -Y^-1 rnea[:6])."""
     import qrw_hip
 
-    B = 16
-    sb = synth_mod.SyntheticBatch(B, 16, gaits=("trot",), seed0=93000)
+    calls, ref = wr.family("patterns", synth_mod), wr.oracle_run(oracle_mod, synth_mod, "patterns")
+    ref_w, _ = wr.oracle_analysis(oracle_mod, synth_mod, "patterns")
+    B = len(calls[0]["q"])
+    assert B == 16 and {tuple(c) for d in calls for c in d["contacts"].astype(int)} == {tuple((n >> i) & 1 for i in range(4)) for n in range(16)}
     eng = qrw_hip.Batch(B)
     eng.wbc_set_lanes(lanes)
-    refs = [oracle_mod.WbcController(0.002) for _ in range(B)]
-    rng = np.random.default_rng(5)
-    for s in range(4):
-        d = sb.step(s)
-        contacts = np.array([[(((b + 5 * s) % 16) >> i) & 1 for i in range(4)] for b in range(B)], dtype=np.float64)
-        f = f_cmd_for(contacts, rng)
-        o = eng.wbc_compute_host(d["q"], d["dq"], f, contacts, d["pgoals"], d["vgoals"], d["agoals"])
+    big, got_w = {}, []
+    for s, (d, r) in enumerate(zip(calls, ref)):
+        contacts = d["contacts"]
+        o = eng.wbc_compute_host(d["q"], d["dq"], d["f_cmd"], contacts, d["pgoals"], d["vgoals"], d["agoals"])
         st = eng.wbc_stats()
         for b in range(B):
-            r = refs[b]
-            r.compute(d["q"][b], d["dq"][b], f[b], contacts[b], d["pgoals"][b], d["vgoals"][b], d["agoals"][b])
-            assert st["iters"][b] == r.qp_iter, (s, b, contacts[b], st["iters"][b], r.qp_iter)
-            for key, ref in (("tau_ff", r.tau_ff), ("qdes", r.qdes), ("vdes", r.vdes[:, 0]),
-                             ("f_with_delta", r.f_with_delta[:, 0]), ("ddq_res", r.ddq_res)):
-                assert rel_err(o[key][b], ref) < RTOL, (s, b, key, contacts[b])
+            assert st["iters"][b] == r["iters"][b], (s, b, contacts[b], st["iters"][b], r["iters"][b])
+            for key in ("tau_ff", "qdes", "vdes", "f_with_delta", "ddq_res"):
+                assert rel_err(o[key][b], r[key][b]) < RTOL, (s, b, key, contacts[b])
+        got_w.append(wr.batch_worst(oracle_mod, d, o, xstar=ref_w[s]["xstar"]))
+        big = _worse(big, wr.check("patterns", got_w[-1], (s, lanes)))
+    _report("patterns", lanes, big, wr.check_optimum(got_w, ref_w, (lanes,)))
 
 
 def _full_size_pipeline(synth_mod, B, N, gaits, seed0, steps=3):
@@ -464,12 +479,19 @@ def test_wbc_on_wild_inputs_matches_oracle(oracle_mod, synth_mod, lanes):
     differs at 1e-6 ... 1e-3 (all inside the QP's own 1e-5 tolerances): the reference built twice would do the same.  So both oracle
     builds run beside the kernel; a robot counts as ROUNDING-SENSITIVE from the first call on at which the two builds disagree
     (rho or any output beyond 1e-9, or the iteration count).  Every other robot must take the oracle's iteration count and match
-    it to 1e-4 (measured <= 4e-9); a sensitive one must stay within 1e-2 and one termination check (25 iterations); status solved
-    and k_since_contact exact for all.  At least 70 % of the robots must still be insensitive after the ten calls."""
+    it to 1e-4 (measured <= 4e-9) in tau_ff, f_with_delta and ddq_res; a sensitive one must stay within 1e-2 and one termination
+    check (25 iterations); status solved and k_since_contact exact for all.  At least 70 % of the robots must still be insensitive
+    after the ten calls.
+
+    What does NOT depend on the path the ADMM iteration took is held to rounding level on EVERY robot, the sensitive ones included
+    (tests/wbc_recompose.py): qdes, vdes and feet against the oracle's inverse kinematics, ddq_res and tau_ff against the oracle's
+    rigid-body pieces evaluated at the kernel's own f -- each within 100 x the oracle's one-ulp spread, absolute -- and f itself
+    within 2 x the strict oracle's largest distance to the QP's one optimum over the run (likewise its violation of the bounds)."""
     import qrw_hip
 
     B, K = 144, 10
-    gen = synth_mod.RandomWbcInputs(B, seed0=20700000 + lanes)
+    fam = "wild%d" % lanes
+    calls = wr.family(fam, synth_mod)  # synth.RandomWbcInputs(144, seed0=20700000 + lanes)
     eng = qrw_hip.Batch(B)
     eng.wbc_set_lanes(lanes)
     oracle_mod.build(fast=True)
@@ -488,8 +510,9 @@ def test_wbc_on_wild_inputs_matches_oracle(oracle_mod, synth_mod, lanes):
     pats, bound, its = set(), 0, []
     sensitive = np.zeros(B, bool)
     worst_clean = worst_sens = 0.0
+    big, got_w, ref_w = {}, [], []
     for c in range(K):
-        d = gen.step(c)
+        d = calls[c]
         args = (d["q"], d["dq"], d["f_cmd"], d["contacts"], d["pgoals"], d["vgoals"], d["agoals"])
         o = eng.wbc_compute_host(*args)
         ra, rb = ref.compute(*args, threads), ref2.compute(*args, threads)
@@ -501,10 +524,17 @@ def test_wbc_on_wild_inputs_matches_oracle(oracle_mod, synth_mod, lanes):
             ref._lib.wbc_oracle_get_k_since_contact(h, ksc[b].ctypes.data_as(dp))
         assert np.array_equal(st["k_since_contact"], ksc), c
         sensitive |= (dev(rb, ra) > 1e-9) | (it != it2) | (np.abs(rho2 / rho - 1) > 1e-9)
-        e = dev((o["tau_ff"], o["qdes"], o["vdes"], o["f_with_delta"]), ra)
+        e = dev((o["tau_ff"], o["f_with_delta"]), (ra[0], ra[3]))
         clean = ~sensitive
         assert np.array_equal(st["iters"][clean], it[clean]), (c, np.nonzero(clean & (st["iters"] != it))[0][:8])
         assert (e[clean] < RTOL).all(), (c, np.nonzero(clean & (e >= RTOL))[0][:8], e[clean].max())
+        e_dd = dev((o["ddq_res"],), (ref.ddq_res(),))
+        assert (e_dd[clean] < RTOL).all(), (c, np.nonzero(clean & (e_dd >= RTOL))[0][:8], e_dd[clean].max())
+        # split at the QP, on all robots; the strict oracle's own distance to the optimum beside the kernel's
+        ro = dict(tau_ff=ra[0], qdes=ra[1], vdes=ra[2], f_with_delta=ra[3], ddq_res=ref.ddq_res(), feet=ref.feet())
+        ref_w.append(wr.batch_worst(oracle_mod, d, ro))
+        got_w.append(wr.batch_worst(oracle_mod, d, o, xstar=ref_w[-1]["xstar"]))
+        big = _worse(big, wr.check(fam, got_w[-1], (c, lanes)))
         assert (np.abs(st["iters"][sensitive] - it[sensitive]) <= 25).all() and (e[sensitive] < 1e-2).all(), (c, e[sensitive].max() if sensitive.any() else 0)
         worst_clean = max(worst_clean, float(e[clean].max()))
         worst_sens = max(worst_sens, float(e[sensitive].max()) if sensitive.any() else 0.0)
@@ -516,3 +546,85 @@ def test_wbc_on_wild_inputs_matches_oracle(oracle_mod, synth_mod, lanes):
           "deviation %.2e on the others, %.2e on the sensitive ones; QP iterations %d..%d, %d contact sets, %d forces on the 25 N bound"
           % (lanes, int(sensitive.sum()), B, K, worst_clean, worst_sens, its.min(), its.max(), len(pats), bound))
     assert len(pats) == 16 and its.max() >= 150 and sensitive.mean() <= 0.30
+    _report(fam, lanes, big, wr.check_optimum(got_w, ref_w, (lanes,)))
+
+
+@LANES
+def test_a_robots_step_does_not_depend_on_its_position(synth_mod, lanes):
+    """One robot's wild input sequence at batch positions 0, 3, 4, 15, 16 and B - 1 of a B = 83 handle (first and last robot of a
+    wavefront of either kernel form, both sides of the boundary between two, the last robot of the padded last wavefront), among
+    neighbours that all differ: outputs, iteration count, status, rho and k_since_contact bit-identical at every position on each
+    of six warm-started calls."""
+    import qrw_hip
+
+    B, K = 83, 6
+    pos = [0, 3, 4, 15, 16, B - 1]
+    one, others = synth_mod.RandomWbcInputs(1, seed0=20710000), synth_mod.RandomWbcInputs(B, seed0=20720000)
+    eng = qrw_hip.Batch(B)
+    eng.wbc_set_lanes(lanes)
+    its = []
+    rest = np.setdiff1d(np.arange(B), pos)
+    for c in range(K):
+        d, r = others.step(c), one.step(c)
+        for k in wr.INPUT_KEYS:
+            d[k][pos] = r[k][0]
+        o = eng.wbc_compute_host(*[d[k] for k in wr.INPUT_KEYS])
+        st = eng.wbc_stats()
+        assert (st["status"] == 1).all() and all(np.isfinite(v).all() for v in o.values()), c
+        for p in pos[1:]:
+            for k in o:
+                assert np.array_equal(o[k][p], o[k][pos[0]]), (c, p, k)
+            for k in st:
+                assert np.array_equal(st[k][p], st[k][pos[0]]), (c, p, k)
+        assert (np.abs(o["tau_ff"][rest] - o["tau_ff"][pos[0]]).max(1) > 1e-3).all()  # the neighbours are other robots
+        its.append(st["iters"][rest])
+    assert len(set(np.concatenate(its).tolist())) >= 3  # neighbours that stop at other termination checks than the robot under test
+
+
+@LANES
+def test_null_outputs_leave_the_rest_unchanged(synth_mod, lanes):
+    """include/qrw_hip.h: "any output may be NULL" -- qrw_wbc_compute through the raw entry (the wrappers always allocate): NULL for
+    each of the six outputs in turn and for all six at once, on a handle of its own each, on the first two of three warm-started calls
+    on wild inputs (B = 21); the third call asks for all six.  The outputs that were asked for, qrw_wbc_get_stats after each call and the next call's outputs (the warm start: the
+    solver state was written whatever was asked for) are bit-identical to a handle that asked for all six; a NULL output's buffer
+    keeps what it held."""
+    import ctypes as C
+
+    import torch
+
+    import qrw_hip
+
+    B = 21
+    names = ("tau_ff", "qdes", "vdes", "f_with_delta", "ddq_res", "feet")
+    shapes = dict(tau_ff=(B, 12), qdes=(B, 19), vdes=(B, 18), f_with_delta=(B, 12), ddq_res=(B, 6), feet=(B, 3, 3, 4))
+    gen = synth_mod.RandomWbcInputs(B, seed0=20730000)
+    calls = [gen.step(c) for c in range(3)]
+    lib = qrw_hip.load_library()
+    variants = [()] + [(n,) for n in names] + [names]
+    runs = []
+    for null in variants:
+        eng = qrw_hip.Batch(B)
+        eng.wbc_set_lanes(lanes)
+        seen = []
+        for c, d in enumerate(calls):
+            ins = [torch.from_numpy(np.ascontiguousarray(d[k])).cuda() for k in wr.INPUT_KEYS]
+            outs = {n: torch.full(shapes[n], -7.25, dtype=torch.float64, device="cuda") for n in names}
+            skip = null if c < 2 else ()  # the third call asks for everything: it shows the state the first two left
+            ptrs = [C.c_void_p(None) if n in skip else C.c_void_p(outs[n].data_ptr()) for n in names]
+            rc = lib.qrw_wbc_compute(eng._handle, *[C.c_void_p(t.data_ptr()) for t in ins], *ptrs,
+                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            assert rc == 0, (null, c, lib.qrw_last_error())
+            torch.cuda.synchronize()
+            seen.append(({n: outs[n].cpu().numpy() for n in names}, eng.wbc_stats(), skip))
+        runs.append(seen)
+    full = runs[0]
+    assert all(np.isfinite(v).all() and (v != -7.25).any() for o, _, _ in full for v in o.values())
+    for null, seen in zip(variants[1:], runs[1:]):
+        for c, ((o, st, skip), (o0, st0, _)) in enumerate(zip(seen, full)):
+            for n in names:
+                if n in skip:
+                    assert (o[n] == -7.25).all(), (null, c, n)
+                else:
+                    assert np.array_equal(o[n], o0[n]), (null, c, n)
+            for k in st0:
+                assert np.array_equal(st[k], st0[k]), (null, c, k)
