@@ -466,6 +466,72 @@ int qrw_sim_set_terrain_host(qrw_handle h, const double *h_heights, int32_t rows
                              double dy, const double *h_origin_xy);
 int qrw_sim_clear_terrain(qrw_handle h);
 
+/* ---------------- joystick: the tick in, reference velocity, gait code and push out ----------------
+ * The first line of the reference's control iteration, Joystick.update_v_ref(k, velID) (scripts/Controller.py:210), as a device
+ * stage with per-robot scenarios: its outputs are the d_joy_vref operand of qrw_controller_update_state / qrw_control_pre /
+ * qrw_iteration_bind, the d_code operand of the planners and the d_f_ext operand of qrw_sim_step.  Stateless in the tick: but for
+ * the gamepad filter and the stop latch every output is a function of k and the tables alone.  The velocity comes from ONE of
+ *   QRW_JOY_PROFILE  handle_v_switch / apply_velocity_change (scripts/Joystick.py:160-190): cubic blends between the columns of a
+ *                    per-robot switch table; after the last switch the value of the tick before it is held, as the reference does;
+ *   QRW_JOY_RAMP     update_v_ref_multi_simu (:289-315): (Vx, Vy, Vw) ramped from tick k_start over beta = (int) max(|V| 10000,
+ *                    100) ticks (2500 for Vw);
+ *   QRW_JOY_GAMEPAD  the low-pass filter of update_v_ref_gamepad with its dead band (:135-137) on the command given to every step;
+ * the codes are computeCode's one-shot (:144-158) from a schedule of (tick, code) pairs -- `code` on that tick, 0 on every other,
+ * the later pair wins on equal ticks -- and the pushes are apply_external_force (scripts/PyBulletSimulator.py:402-431): the sum, in
+ * table order, of alpha [F; M] over the entries with start <= k <= start + duration.  Departure: that wrench is the simulator's
+ * world wrench at the base origin, not Bullet's LINK_FRAME.  Not provided: the gamepad client, the `reduced` flag, joystick.stop
+ * reaching the controller's security branch, the velID tables (callers pass their own).
+ * Limits (the integer powers of the polynomials must be exact in a double): two consecutive switches are at most 2^17 ticks apart,
+ * k_switch is non-decreasing and starts at or before tick 0, a push lasts 1 .. 2^13 ticks, |V| 10000 < 2^31; ticks are >= 0.
+ * A table shorter than the fleet's common length is padded: a profile by repeating its last column, the codes with a negative
+ * tick, the pushes with a window before tick 0 -- none of which changes a bit of the outputs. */
+#define QRW_JOY_PROFILE 0
+#define QRW_JOY_RAMP 1
+#define QRW_JOY_GAMEPAD 2
+typedef struct {
+  int32_t mode;       /* QRW_JOY_PROFILE, QRW_JOY_RAMP or QRW_JOY_GAMEPAD                                          */
+  int32_t n_switch;   /* profile: columns per robot, 1..32 (1: zeros)                                              */
+  int32_t n_codes;    /* (tick, code) pairs per robot, 0..16                                                       */
+  int32_t n_pushes;   /* pushes per robot, 0..8                                                                    */
+  int32_t k_start;    /* ramp: first tick of the ramps (the reference's k_mpc * 16 * 3)                            */
+  double gp_alpha;    /* gamepad: filter coefficient in (0, 1]; the reference's is the quotient 0.0020 / 0.02      */
+  double gp_deadband; /* gamepad: components with -band < v < band become 0; >= 0, the reference's is 0.005        */
+} qrw_joystick_config;
+/* HOST pointers, robot-major (what a caller writes down per robot); a table its mode or its count does not use may be NULL */
+typedef struct {
+  const int32_t *k_switch;   /* [B][n_switch]                      */
+  const double *v_switch;    /* [B][6][n_switch]                   */
+  const double *ramp_v;      /* [B][3] Vx, Vy, Vw                  */
+  const int32_t *code_k;     /* [B][n_codes] ticks                 */
+  const int32_t *code_v;     /* [B][n_codes] codes                 */
+  const int32_t *push_k;     /* [B][n_pushes][2] start, duration   */
+  const double *push_w;      /* [B][n_pushes][6] F (3), M (3)      */
+} qrw_joystick_tables;
+/* Replaces Joystick.__init__ (scripts/Joystick.py:14-58) and update_for_analysis (:317-326) / the tables of
+ * update_v_ref_predefined (:201-284).  A set-up call: the tables are validated on the host before anything is launched (-1, with
+ * the offending robot and entry in qrw_last_error(); the handle keeps what it had), the handle owns device copies (item-major),
+ * and the state -- the filter's v_ref zero, k_stop -1 -- is written by a launch on `stream`.  Synchronised per handle (state family
+ * "joystick").  Again = re-initialise: afterwards the state is a fresh handle's, bit for bit.  The first call allocates the state
+ * (7 doubles per robot), which qrw_state_bytes counts from then on; a handle that never calls it allocates nothing. */
+int qrw_joystick_init(qrw_handle h, const qrw_joystick_config *cfg, const qrw_joystick_tables *tables, void *stream);
+/* Replaces Joystick.update_v_ref(k, velID) (scripts/Joystick.py:60-79) and the apply_external_force calls of a tick
+ * (scripts/PyBulletSimulator.py:354-356) for tick k >= 0.  Only enqueues.
+ *   in : d_v_gp [B][6] this tick's unfiltered command: required in gamepad mode, NULL otherwise; d_stop [B] int32 or NULL (in a
+ *        fleet the controller's d_error_flag): the first tick on which d_stop[b] != 0 becomes the robot's k_stop, and from that
+ *        tick on its three outputs are zero and its filter state is frozen, also when the flag is cleared again (the reference
+ *        leaves its loop at the first error, scripts/main_solo12_control.py:180)
+ *   out: d_joy_vref [B][6]; d_code [B] int32 or NULL; d_f_ext [B][6]: required when the handle has pushes (zeros while none is
+ *        active), optional (zeros) otherwise */
+int qrw_joystick_step(qrw_handle h, int32_t k, const double *d_v_gp, const int32_t *d_stop, double *d_joy_vref, int32_t *d_code,
+                      double *d_f_ext, void *stream);
+/* The same with host buffers, synchronised per handle. */
+int qrw_joystick_step_host(qrw_handle h, int32_t k, const double *h_v_gp, const int32_t *h_stop, double *h_joy_vref,
+                           int32_t *h_code, double *h_f_ext);
+/* Getter of the joystick state (the reference's Joystick.v_ref in gamepad mode; the outcome `finished` of control_loop,
+ * scripts/main_solo12_control.py:180,239, per robot): which = 0 the filter's v_ref of robot b (count <= 6 doubles), 1 k_stop of
+ * the robots b .. b + count - 1 (-1: never stopped). */
+int qrw_joystick_get_host(qrw_handle h, int32_t which, int32_t b, int32_t count, double *h_out);
+
 /* ---------------- asynchronous MPC ----------------
  * The reference runs the MPC in a child process on its own CPU core and polls a shared flag
  * (scripts/MPC_Wrapper.py:150-298).  Here the MPC gets its own HIP stream restricted to a subset of the compute

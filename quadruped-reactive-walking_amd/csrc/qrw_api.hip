@@ -7,6 +7,7 @@
 
 #include "../../include/qrw_solo12_model.h"
 #include "gait_masks.h"
+#include "joystick_kernel.h"
 #include "kalman_filter.h"
 #include "qrw_host.h"
 
@@ -175,12 +176,12 @@ extern "C" int qrw_destroy(qrw_handle h) {
 }
 
 // (the persistent solver state of the MPC and the WBC and the estimator's filters -- the Kalman filter's once a handle has
-// allocated it: not the diagnostics, planner, controller, staging or queue buffers)
+// allocated it, the joystick stage's likewise: not the diagnostics, planner, controller, staging or queue buffers)
 extern "C" int64_t qrw_state_bytes(qrw_handle h) {
   if (!h) return 0;
   return (int64_t)(h->mpc_st.bytes + h->mpc_gait.bytes + h->mpc_flags.bytes + h->mpc_iters.bytes + h->mpc_status.bytes +
                    h->mpc_rho_updates.bytes + h->mpc_order.bytes + h->mpc_ema.bytes + h->mpc_rho.bytes + h->mpc_pri.bytes +
-                   h->mpc_dua.bytes + h->wbc_st.bytes + h->wbc_iters.bytes + h->wbc_status.bytes + h->est_st.bytes + h->kal_st.bytes + h->sim_st.bytes);
+                   h->mpc_dua.bytes + h->wbc_st.bytes + h->wbc_iters.bytes + h->wbc_status.bytes + h->est_st.bytes + h->kal_st.bytes + h->sim_st.bytes + h->joy_st.bytes);
 }
 
 // what every MPC launch of a handle is told about its persistent state; xref / fsteps / out as the caller lays them out
@@ -1142,6 +1143,177 @@ extern "C" int qrw_sim_set_terrain_host(qrw_handle h, const double* h_heights, i
 extern "C" int qrw_sim_clear_terrain(qrw_handle h) {
   if (!h) return fail(-1, "qrw_sim_clear_terrain: null handle");
   h->sim_terrain_on = h->sim_origin_on = false;  // (the buffers stay for the next qrw_sim_set_terrain of the same size)
+  return 0;
+}
+
+// ------------------------------------------------------------------ joystick stage (joystick_kernel.hip)
+// what every joystick launch of a handle is told: the configuration and the item-major tables carved out of joy_ti / joy_td
+static qrw::JoystickArgs joystick_common(qrw_handle h) {
+  qrw::JoystickArgs a;
+  memset(&a, 0, sizeof(a));
+  const qrw_joystick_config& c = h->jcfg;
+  const size_t B = h->cfg.batch;
+  const size_t ns = c.mode == QRW_JOY_PROFILE ? c.n_switch : 0, nc = c.n_codes, np = c.n_pushes;
+  a.t.B = h->cfg.batch; a.t.n_switch = (int)ns; a.t.n_codes = c.n_codes; a.t.n_pushes = c.n_pushes;
+  a.t.k_start = c.k_start; a.t.gp_alpha = c.gp_alpha; a.t.gp_deadband = c.gp_deadband;
+  int32_t* ti = h->joy_ti;
+  a.t.k_switch = ti; ti += ns * B;
+  a.t.code_k = ti; ti += nc * B;
+  a.t.code_v = ti; ti += nc * B;
+  a.t.push_start = ti; ti += np * B;
+  a.t.push_dur = ti;
+  double* td = h->joy_td;
+  a.t.v_switch = td; td += ns * 6 * B;
+  a.t.ramp_v = td; td += 3 * B;
+  a.t.push_w = td;
+  a.st = h->joy_st;
+  return a;
+}
+
+// Joystick.__init__ (scripts/Joystick.py:14-58) + update_for_analysis (:317-326) / the tables of update_v_ref_predefined (:201-284)
+extern "C" int qrw_joystick_init(qrw_handle h, const qrw_joystick_config* cfg, const qrw_joystick_tables* tab, void* stream) {
+  QRW_ENTER_HOST(h, !cfg || !tab, "qrw_joystick_init: null argument");
+  namespace joy = qrw::joy;
+  char text[256];
+  auto refuse = [&](const char* what) { return fail(-1, (std::string("qrw_joystick_init: ") + what).c_str()); };
+  const int B = h->cfg.batch;
+  // ---- validation, on the host, before anything is allocated, copied or launched
+  if (cfg->mode != QRW_JOY_PROFILE && cfg->mode != QRW_JOY_RAMP && cfg->mode != QRW_JOY_GAMEPAD)
+    return refuse("mode must be QRW_JOY_PROFILE, QRW_JOY_RAMP or QRW_JOY_GAMEPAD");
+  if (cfg->n_codes < 0 || cfg->n_codes > joy::kMaxCodes) return refuse("n_codes must be in 0..16");
+  if (cfg->n_pushes < 0 || cfg->n_pushes > joy::kMaxPushes) return refuse("n_pushes must be in 0..8");
+  if (cfg->n_codes && (!tab->code_k || !tab->code_v)) return refuse("n_codes > 0 needs code_k and code_v");
+  if (cfg->n_pushes && (!tab->push_k || !tab->push_w)) return refuse("n_pushes > 0 needs push_k and push_w");
+  const int ns = cfg->mode == QRW_JOY_PROFILE ? cfg->n_switch : 0, nc = cfg->n_codes, np = cfg->n_pushes;
+  if (cfg->mode == QRW_JOY_PROFILE) {
+    if (ns < 1 || ns > joy::kMaxSwitch) return refuse("n_switch must be in 1..32");
+    if (!tab->k_switch || !tab->v_switch) return refuse("profile mode needs k_switch and v_switch");
+    for (int b = 0; b < B; b++) {
+      int entry = 0;
+      const int bad = joy::check_profile(tab->k_switch + (size_t)b * ns, ns, &entry);
+      if (!bad) continue;
+      snprintf(text, sizeof(text), "robot %d, k_switch entry %d: %s", b, entry,
+               bad == joy::kBadFirst ? "the table must start at or before tick 0"
+               : bad == joy::kBadDecreasing ? "decreasing (k_switch must be non-decreasing)"
+                                            : "more than 2^17 ticks after the entry before it (t1^3 must be exact in a double)");
+      return refuse(text);
+    }
+  } else if (cfg->mode == QRW_JOY_RAMP) {
+    if (!tab->ramp_v) return refuse("ramp mode needs ramp_v");
+    for (int b = 0; b < B; b++) {
+      int entry = 0;
+      if (joy::check_ramp(tab->ramp_v + (size_t)b * 3, &entry)) {
+        snprintf(text, sizeof(text), "robot %d, ramp_v entry %d: not finite, or |V| x scale does not fit an int32", b, entry);
+        return refuse(text);
+      }
+    }
+  } else {
+    if (!(cfg->gp_alpha > 0.0 && cfg->gp_alpha <= 1.0)) return refuse("gp_alpha must be in (0, 1]");
+    if (!(cfg->gp_deadband >= 0.0) || !std::isfinite(cfg->gp_deadband)) return refuse("gp_deadband must be >= 0 and finite");
+  }
+  std::vector<int32_t> dur((size_t)np);
+  for (int b = 0; b < B && np; b++) {
+    for (int e = 0; e < np; e++) dur[e] = tab->push_k[((size_t)b * np + e) * 2 + 1];
+    int entry = 0;
+    if (joy::check_push(dur.data(), np, &entry)) {
+      snprintf(text, sizeof(text), "robot %d, push entry %d: duration %d is not in 1..2^13 (t1^4 must be exact in a double)", b, entry,
+               dur[entry]);
+      return refuse(text);
+    }
+  }
+  // ---- the item-major copies ([entry][B], [entry][6][B]), in the order joystick_common carves them
+  const size_t Bz = (size_t)B;
+  std::vector<int32_t> ti(((size_t)ns + 2 * (size_t)nc + 2 * (size_t)np) * Bz + 1);
+  std::vector<double> td(((size_t)ns * 6 + 3 + (size_t)np * 6) * Bz);
+  int32_t *ksw = ti.data(), *ck = ksw + ns * Bz, *cv = ck + nc * Bz, *ps = cv + nc * Bz, *pd = ps + np * Bz;
+  double *vsw = td.data(), *rv = vsw + (size_t)ns * 6 * Bz, *pw = rv + 3 * Bz;
+  for (size_t b = 0; b < Bz; b++) {
+    for (int i = 0; i < ns; i++) {
+      ksw[i * Bz + b] = tab->k_switch[b * ns + i];
+      for (int c = 0; c < 6; c++) vsw[((size_t)i * 6 + c) * Bz + b] = tab->v_switch[(b * 6 + c) * ns + i];
+    }
+    for (int c = 0; c < 3; c++) rv[c * Bz + b] = cfg->mode == QRW_JOY_RAMP ? tab->ramp_v[b * 3 + c] : 0.0;
+    for (int e = 0; e < nc; e++) {
+      ck[e * Bz + b] = tab->code_k[b * nc + e];
+      cv[e * Bz + b] = tab->code_v[b * nc + e];
+    }
+    for (int e = 0; e < np; e++) {
+      ps[e * Bz + b] = tab->push_k[(b * np + e) * 2];
+      pd[e * Bz + b] = tab->push_k[(b * np + e) * 2 + 1];
+      for (int c = 0; c < 6; c++) pw[((size_t)e * 6 + c) * Bz + b] = tab->push_w[(b * np + e) * 6 + c];
+    }
+  }
+  // no step in flight reads the tables while they are replaced (hipFree waits for the device besides)
+  HIP_OK(wait_family(h, kFamJoy), "qrw_joystick_init: earlier joystick step of this handle");
+  h->joy_ready = false;
+  if (!h->joy_st) HIP_OK(h->joy_st.alloc(Bz * qrw::kJoyStItems), "qrw_joystick_init: hipMalloc joy_st");  // (the init launch writes every item)
+  if (h->joy_ti.count() != ti.size()) HIP_OK(h->joy_ti.alloc(ti.size()), "qrw_joystick_init: hipMalloc joy_ti");
+  if (h->joy_td.count() != td.size()) HIP_OK(h->joy_td.alloc(td.size()), "qrw_joystick_init: hipMalloc joy_td");
+  HIP_OK(h2d(h, h->joy_ti.p, ti.data(), ti.size() * sizeof(int32_t)), "qrw_joystick_init: H2D tables");
+  HIP_OK(h2d(h, h->joy_td.p, td.data(), td.size() * sizeof(double)), "qrw_joystick_init: H2D tables");
+  HIP_OK(host_done(h), "qrw_joystick_init: H2D tables");
+  h->jcfg = *cfg;
+  qrw::JoystickArgs a = joystick_common(h);
+  a.init = 1;
+  if (qrw::joystick_launch(a, cfg->mode, (hipStream_t)stream) != 0) return fail(-11, "qrw_joystick_init: launch failed", hipGetLastError());
+  note_launch(h, kFamJoy, (hipStream_t)stream);
+  h->joy_ready = true;
+  return 0;
+}
+
+// Joystick.update_v_ref(k_loop, velID) (scripts/Joystick.py:60-79) + apply_external_force (scripts/PyBulletSimulator.py:402-431)
+extern "C" int qrw_joystick_step(qrw_handle h, int32_t k, const double* d_v_gp, const int32_t* d_stop, double* d_joy_vref,
+                                 int32_t* d_code, double* d_f_ext, void* stream) {
+  QRW_ENTER(h, !h->joy_ready, "qrw_joystick_step: joystick not initialised");
+  if (k < 0) return fail(-1, "qrw_joystick_step: k must be >= 0");
+  if (!d_joy_vref) return fail(-1, "qrw_joystick_step: null output d_joy_vref");
+  if (h->jcfg.mode == QRW_JOY_GAMEPAD ? !d_v_gp : d_v_gp != nullptr)
+    return fail(-1, h->jcfg.mode == QRW_JOY_GAMEPAD ? "qrw_joystick_step: gamepad mode needs d_v_gp"
+                                                     : "qrw_joystick_step: d_v_gp given to a joystick that is not in gamepad mode");
+  if (h->jcfg.n_pushes && !d_f_ext) return fail(-1, "qrw_joystick_step: the handle has pushes: d_f_ext must not be NULL");
+  qrw::JoystickArgs a = joystick_common(h);
+  a.k = k; a.v_gp = d_v_gp; a.stop = d_stop; a.joy_vref = d_joy_vref; a.code = d_code; a.f_ext = d_f_ext;
+  if (qrw::joystick_launch(a, h->jcfg.mode, (hipStream_t)stream) != 0) return fail(-11, "qrw_joystick_step: launch failed", hipGetLastError());
+  note_launch(h, kFamJoy, (hipStream_t)stream);
+  return 0;
+}
+
+extern "C" int qrw_joystick_step_host(qrw_handle h, int32_t k, const double* h_v_gp, const int32_t* h_stop, double* h_joy_vref,
+                                      int32_t* h_code, double* h_f_ext) {
+  QRW_ENTER_HOST(h, !h->joy_ready, "qrw_joystick_step_host: joystick not initialised");
+  if (!h_joy_vref) return fail(-1, "qrw_joystick_step_host: null output h_joy_vref");
+  const size_t B = h->cfg.batch;
+  HIP_OK(wait_family(h, kFamJoy), "qrw_joystick_step_host: earlier joystick step of this handle");
+  Stager s(h);
+  const double* gp = h_v_gp ? s.in(h_v_gp, B * 6) : nullptr;
+  double* vr = s.out(B * 6);
+  double* fe = (h_f_ext || h->jcfg.n_pushes) ? s.out(B * 6) : nullptr;
+  // (the two int32 rows ride in the doubles' staging area)
+  int32_t* st = h_stop ? (int32_t*)s.out((B + 1) / 2) : nullptr;
+  int32_t* cd = h_code ? (int32_t*)s.out((B + 1) / 2) : nullptr;
+  if (!s.ok) return fail(-12, "qrw_joystick_step_host: staging failed");
+  if (st) HIP_OK(h2d(h, st, h_stop, B * sizeof(int32_t)), "qrw_joystick_step_host: H2D stop flags");
+  if (const int rc = qrw_joystick_step(h, k, gp, st, vr, cd, fe, (void*)h->host_stream)) return rc;
+  if (!(s.back(h_joy_vref, vr, B * 6) && s.back(h_f_ext, fe, B * 6))) return fail(-12, "qrw_joystick_step_host: D2H failed");
+  if (cd) HIP_OK(d2h(h, h_code, cd, B * sizeof(int32_t)), "qrw_joystick_step_host: D2H codes");
+  HIP_OK(host_done(h), "qrw_joystick_step_host sync");
+  return 0;
+}
+
+// Joystick.v_ref of the gamepad filter; the outcome of control_loop (scripts/main_solo12_control.py:180,239) per robot
+extern "C" int qrw_joystick_get_host(qrw_handle h, int32_t which, int32_t b, int32_t count, double* h_out) {
+  QRW_ENTER_HOST(h, !h_out || b < 0 || b >= h->cfg.batch || count < 1, "qrw_joystick_get_host: bad argument");
+  if (!h->joy_ready) return fail(-1, "qrw_joystick_get_host: joystick not initialised");
+  const size_t B = h->cfg.batch;
+  if (which == 1) {  // (state items are [item][B]: the k_stop of consecutive robots are consecutive doubles)
+    if (count > h->cfg.batch - b) return fail(-1, "qrw_joystick_get_host: bad item");
+    return read_back(h, kFamJoy, "qrw_joystick_get_host", {{h_out, h->joy_st + (size_t)qrw::kJsKstop * B + b, (size_t)count * sizeof(double)}});
+  }
+  if (which != 0 || count > 6) return fail(-1, "qrw_joystick_get_host: bad item");
+  HIP_OK(wait_family(h, kFamJoy), "qrw_joystick_get_host: earlier joystick step of this handle");
+  HIP_OK(hipMemcpy2DAsync(h_out, sizeof(double), h->joy_st + (size_t)qrw::kJsVref * B + b, B * sizeof(double), sizeof(double), count,
+                          hipMemcpyDeviceToHost, h->host_stream), "qrw_joystick_get_host: D2H joystick state");
+  HIP_OK(host_done(h), "qrw_joystick_get_host: D2H joystick state");
   return 0;
 }
 

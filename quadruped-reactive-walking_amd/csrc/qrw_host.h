@@ -72,7 +72,7 @@ struct PinnedWord {
 
 // state families of a handle: which launches a getter has to wait for
 // (the controller-glue kernels write state no getter reads: their launches are not tracked)
-enum Family { kFamNone = -1, kFamMpc = 0, kFamWbc = 1, kFamPlan = 2, kFamEst = 3, kFamSim = 4, kFamCount = 5 };
+enum Family { kFamNone = -1, kFamMpc = 0, kFamWbc = 1, kFamPlan = 2, kFamEst = 3, kFamSim = 4, kFamJoy = 5, kFamCount = 6 };
 
 }  // namespace qrw::host
 
@@ -130,6 +130,12 @@ struct qrw_handle_s {
   int sim_t_rows = 0, sim_t_cols = 0;
   double sim_t_x0 = 0.0, sim_t_y0 = 0.0, sim_t_dx = 0.0, sim_t_dy = 0.0;
   bool sim_terrain_on = false, sim_origin_on = false;
+  // joystick stage (qrw_joystick_init): its state (allocated by the first init), the handle's item-major copies of the tables
+  // (reallocated only when their size changes) and the configuration they were validated against
+  DevBuf<double> joy_st, joy_td;
+  DevBuf<int32_t> joy_ti;
+  qrw_joystick_config jcfg;
+  bool joy_ready = false;
   // staging for the host-buffer entry points
   DevBuf<double> stage;
   DevBuf<int32_t> stage_i;

@@ -82,6 +82,22 @@ def sim_params(**params):
                       float(p["foot_radius"]), float(p["base_height"]))
 
 
+# qrw_joystick_config / qrw_joystick_tables (include/qrw_hip.h), field for field
+JOY_PROFILE, JOY_RAMP, JOY_GAMEPAD = 0, 1, 2
+JOY_MAX_SWITCH, JOY_MAX_CODES, JOY_MAX_PUSHES = 32, 16, 8
+JOY_GP_ALPHA, JOY_GP_DEADBAND = 0.0020 / 0.02, 0.005  # (scripts/Joystick.py:27-29, :137; alpha evaluated as that quotient)
+
+
+class _JoystickConfig(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("n_switch", C.c_int32), ("n_codes", C.c_int32), ("n_pushes", C.c_int32),
+                ("k_start", C.c_int32), ("gp_alpha", C.c_double), ("gp_deadband", C.c_double)]
+
+
+class _JoystickTables(C.Structure):
+    _fields_ = [("k_switch", _ip), ("v_switch", _dp), ("ramp_v", _dp), ("code_k", _ip), ("code_v", _ip), ("push_k", _ip),
+                ("push_w", _dp)]
+
+
 class _IterationBuffers(C.Structure):
     """qrw_iteration_buffers (include/qrw_hip.h), field for field."""
     _fields_ = ([(n, C.c_void_p) for n in ("d_joy_vref", "d_q_filt", "d_v_filt", "d_rpy", "d_v_secu", "d_code")]
@@ -156,6 +172,10 @@ SIGNATURES = {
     "qrw_sim_set_terrain": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32] + [C.c_double] * 4 + [_vp, _vp]),
     "qrw_sim_set_terrain_host": (C.c_int, [_vp, _dp, C.c_int32, C.c_int32] + [C.c_double] * 4 + [_dp]),
     "qrw_sim_clear_terrain": (C.c_int, [_vp]),
+    "qrw_joystick_init": (C.c_int, [_vp, C.POINTER(_JoystickConfig), C.POINTER(_JoystickTables), _vp]),
+    "qrw_joystick_step": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qrw_joystick_step_host": (C.c_int, [_vp, C.c_int32, _dp, _ip, _dp, _ip, _dp]),
+    "qrw_joystick_get_host": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "qrw_stream_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)]),
     "qrw_stream_destroy": (C.c_int, [_vp]),
     "qrw_device_cu_count": (C.c_int, [C.c_int32, _ip]),
@@ -867,6 +887,68 @@ class Batch:
                                                        _p(None if f_ext is None else _h(f_ext, (n, 6))), C.byref(prm), _p(a), _p(f)),
                "qrw_test_sim_forward_dynamics")
         return a, f
+
+    # ------------------------------------------------ joystick stage (csrc/joystick_kernel.hip)
+    def joystick_init(self, mode, k_switch=None, v_switch=None, ramp_v=None, k_start=0, gp_alpha=JOY_GP_ALPHA,
+                      gp_deadband=JOY_GP_DEADBAND, code_k=None, code_v=None, push_k=None, push_w=None):
+        """qrw_joystick_init from numpy tables, robot-major and already of the fleet's common lengths (Joystick.Joystick_batch
+        pads per-robot lists): k_switch (B,n_switch) / v_switch (B,6,n_switch) for JOY_PROFILE, ramp_v (B,3) + k_start for
+        JOY_RAMP, gp_alpha / gp_deadband for JOY_GAMEPAD; code_k / code_v (B,n_codes), push_k (B,n_pushes,2) start and duration,
+        push_w (B,n_pushes,6).  Validated by the library (QrwError names the robot and the entry); again = re-initialise."""
+        B = self.B
+        i32 = lambda a, tail: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.int32)).reshape((B,) + tail)
+        f64 = lambda a, tail: None if a is None else _h(a, (B,) + tail)
+        n_switch = 0 if k_switch is None else int(np.asarray(k_switch).reshape(B, -1).shape[1])
+        n_codes = 0 if code_k is None else int(np.asarray(code_k).reshape(B, -1).shape[1])
+        n_pushes = 0 if push_k is None else int(np.asarray(push_k).reshape(B, -1).shape[1] // 2)
+        arrays = [i32(k_switch, (n_switch,)), f64(v_switch, (6, n_switch)), f64(ramp_v, (3,)), i32(code_k, (n_codes,)),
+                  i32(code_v, (n_codes,)), i32(push_k, (n_pushes, 2)), f64(push_w, (n_pushes, 6))]
+        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        tab = _JoystickTables(*[ptr(a, t) for a, (_, t) in zip(arrays, _JoystickTables._fields_)])
+        cfg = _JoystickConfig(int(mode), n_switch, n_codes, n_pushes, int(k_start), float(gp_alpha), float(gp_deadband))
+        _check(self._lib.qrw_joystick_init(self._handle, C.byref(cfg), C.byref(tab), self._stream()), "qrw_joystick_init")
+        self.joystick_mode, self.joystick_pushes = int(mode), n_pushes
+
+    def joystick_step(self, k, v_ref, code=None, f_ext=None, v_gp=None, stop=None):
+        """qrw_joystick_step for tick k: v_ref (B,6) and f_ext (B,6) CUDA float64, code (B,) CUDA int32 are written; v_gp (B,6)
+        is the gamepad command (that mode only), stop (B,) CUDA int32 the stop flags or None.  Enqueues on the current stream."""
+        B = self.B
+        i32 = lambda t: _vp(0) if t is None else self._dev_i32(t)
+        opt = lambda t: _vp(0) if t is None else self._dev(t, (B, 6))
+        _check(self._lib.qrw_joystick_step(self._handle, int(k), opt(v_gp), i32(stop), self._dev(v_ref, (B, 6)), i32(code),
+                                           opt(f_ext), self._stream()), "qrw_joystick_step")
+
+    def _dev_i32(self, t):
+        import torch
+
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+                and tuple(t.shape) == (self.B,) and t.device.index == self.device):
+            raise QrwError("expected a contiguous int32 CUDA tensor of shape (%d,) on cuda:%d" % (self.B, self.device))
+        return _vp(t.data_ptr())
+
+    def joystick_step_host(self, k, v_gp=None, stop=None, want_f_ext=True):
+        """qrw_joystick_step_host with numpy arrays; returns dict(v_ref (B,6), code (B,) int32, f_ext (B,6) or None)."""
+        B = self.B
+        gp = None if v_gp is None else _h(v_gp, (B, 6))
+        st = None if stop is None else np.ascontiguousarray(np.asarray(stop, dtype=np.int32)).reshape(B)
+        o = dict(v_ref=np.empty((B, 6)), code=np.empty(B, np.int32), f_ext=np.empty((B, 6)) if want_f_ext else None)
+        _check(self._lib.qrw_joystick_step_host(self._handle, int(k), _p(gp), None if st is None else st.ctypes.data_as(_ip),
+                                                _p(o["v_ref"]), o["code"].ctypes.data_as(_ip), _p(o["f_ext"])),
+               "qrw_joystick_step_host")
+        return o
+
+    def joystick_get(self, item, b=0):
+        """The joystick state: "v_ref" (6,) the gamepad filter's state of robot b, "k_stop" (B,) int64 the tick at which every
+        robot's stop flag was first seen (-1: never).  Synchronises with the last joystick step of this handle."""
+        if item == "k_stop":
+            out = np.empty(self.B)
+            _check(self._lib.qrw_joystick_get_host(self._handle, 1, 0, self.B, _p(out)), "qrw_joystick_get_host")
+            return out.astype(np.int64)
+        if item != "v_ref":
+            raise QrwError("joystick_get: item must be 'v_ref' or 'k_stop'")
+        out = np.empty(6)
+        _check(self._lib.qrw_joystick_get_host(self._handle, 0, int(b), 6, _p(out)), "qrw_joystick_get_host")
+        return out
 
     # ------------------------------------------------ getters / diagnostics
     def mpc_gait(self, b=0):
