@@ -154,7 +154,7 @@ __device__ __forceinline__ void chain_forward_paired(const double* sN, double* s
   // root: chain A's last step sits in lanes 32..43 (row 2), chain B's contribution (step LB, odd, exchanged) in lanes
   // 48..59 (row 3): a row exchange instead of an LDS round trip
   x += swap_rows16(pB);
-  if (lane >= 32 && lane < 44) sX[m * 12 + i] = x;
+  ps_oddA[m * 12] = x;
 }
 template <int NC>
 __device__ __forceinline__ void chain_backward_paired(const double* sN, double* sX, double* sDump, int lane) {
@@ -271,7 +271,7 @@ __device__ __forceinline__ void chain_forward_quad(const double* sN, double* sX,
   // root: chain A's last step (LA, the fourth of the last quad) sits in lanes 32..43 (row 2), chain B's contribution
   // (step LB, the third, computed in the upper half) in lanes 48..59 (row 3): a row exchange instead of an LDS round trip
   x += swap_rows16(pB);
-  if (lane >= 32 && lane < 44) sX[m * 12 + i] = x;
+  ps_hiA[m * 12] = x;
 }
 template <int NC>
 __device__ __forceinline__ void chain_backward_quad(const double* sN, double* sX, double* sDump, int lane) {
@@ -331,6 +331,8 @@ __device__ __forceinline__ void chain_backward_quad(const double* sN, double* sX
 // sDump: (NC/2 + 2) * 12 doubles of LDS that absorb the stores of lanes / steps that must not write (cheaper than
 // switching EXEC around every store: a lone wavefront pays full issue time for each scalar instruction).  The sweeps
 // above store step t at offset t*12 (forward, t < NC/2) or (NC/2 - t)*12 (backward, t >= 1), whichever half stores it.
+// The forward sweep's root store (lanes 32..43 to sX, everybody else here) uses offset (NC/2)*12: the row NC/2 of this array is
+// in use, the "+ 2" is not slack.
 template <int NC>
 __device__ __forceinline__ void chain_forward(const double* sN, double* sX, double* sDump, int Nrt, int lane) {
   if constexpr (NC > 0 && (NC / 2) % 4 == 0) {

@@ -67,6 +67,16 @@ __device__ __forceinline__ void wg_sync_t() {
   else __syncthreads();
 }
 #define wg_sync() wg_sync_t<NW>()
+
+// A decision of the ADMM loop that is the same in every lane (it derives from a reduction over the whole instance), handed
+// to the compiler as a scalar: the branch on it is then an s_cbranch_scc, not an EXEC mask with its save / restore and an
+// accumulated exited-lanes mask carried through every iteration.  Only ever called with all lanes active.
+__device__ __forceinline__ bool uniform_flag(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
+// A double that is the same in every lane and is only read between the check intervals (rho, the primal residual of the last
+// check), moved to a scalar register pair: it then costs the inner loop no vector registers while it waits.
+__device__ __forceinline__ double uniform_double(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
 #ifdef QRW_PROFILE_PHASES
 #define PH_DECL unsigned long long ph_t0 = __builtin_amdgcn_s_memtime(), ph_acc[10] = {0,0,0,0,0,0,0,0,0,0};
 #ifndef QRW_PH_MASK
@@ -673,7 +683,9 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
   // i-th largest iteration count of the PREVIOUS solve (a good predictor: warm-started receding-horizon problems)
   PH_DECL
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wv = tid >> 6;
+  // (one wavefront per instance: wv is a compile-time 0, so that `if (wv == 0)` around the sweeps folds away instead of
+  // becoming an EXEC mask that is never empty)
+  const int lane = tid & 63, wv = (NW == 1) ? 0 : tid >> 6;
 #ifdef QRW_DEBUG_POISON
   // diagnostic build (scripts/gpu_poison_bisect.py): one member of the LDS struct filled with NaN before anything else runs, the
   // member chosen by the otherwise unused pre_bin -- which unwritten LDS does a solve read?
@@ -718,6 +730,10 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
     }
   } else {
     b = a.order ? a.order[blockIdx.x] : blockIdx.x;
+  }
+  if constexpr (SEQ || PRE) {  // (a task from a queue reaches every lane through the LDS: scalars again, and with them every pointer derived from them)
+    b = __builtin_amdgcn_readfirstlane(b);
+    seq_s = __builtin_amdgcn_readfirstlane(seq_s);
   }
   // PRE: iteration this instance was parked at by an earlier chunk of THIS launch (0: a fresh solve; a workgroup that takes
   // its instance by index starts the solve whatever an aborted launch may have left behind)
@@ -1053,6 +1069,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
 #pragma unroll
   for (int c = 0; c < 5; c++) etC[c] = resumed ? yC[c] : Ec[c] * yC[c];
   // per-lane constants of the current rho (set with every factorisation)
+  // (zeU = Omega_D u: here only for the first iteration's theta; the loop does not carry it, the blocks that read it form it again: QRW_ZETA_U)
   double aOD[3], kD[3], zeU[3], aOS[3], aOC[5], sDx2[3], sDf2[3], lz4 = 0.0;
 #pragma unroll
   for (int t = 0; t < 3; t++) {
@@ -1082,16 +1099,20 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
   const int kr1 = (j < 2) ? j + 4 : j;  // lanes 0,1 of a quad also take rows 4,5 of K^-1 (lanes 2,3: a discarded duplicate)
 
   // =========================== C/D. factor + ADMM loop (OSQP osqp_solve) ===========================
-  bool need_factor = true;
+  // (true on entry, but not to the compiler's knowledge: it would otherwise lay out a second copy of the factorisation ahead
+  // of the loop, fed from the set-up's registers while everything the loop needs is live as well)
+  int need_factor_entry = 1;
+  asm volatile("" : "+s"(need_factor_entry));
+  bool need_factor = need_factor_entry != 0;
   int iter = 0, status = kStatusUnsolved, rho_updates = 0;
   double pri_res = 0.0, dua_res = 0.0, last_np = 0.0, last_nd = 0.0;
   const int max_iter = 4000;
-  rho = fmin(fmax(rho, kRhoMin), kRhoMax);
+  rho = uniform_double(fmin(fmax(rho, kRhoMin), kRhoMax));
   {  // loop variables from the warm start (OSQP's scaled x, z, y of the previous solve, used as they are)
     // (PRE, resumed: rho is the value the solve was parked with, possibly just adapted; the loop constants and zeta_u belong
     // to the rho of the parked factorisation, kept in the cost-scale slot: the factor block below re-bases them exactly as
     // the uninterrupted solve does at this iteration)
-    rho_used = resumed ? ST(kStC) : rho;
+    rho_used = uniform_double(resumed ? ST(kStC) : rho);
     const double rho_eq0 = kRhoEqOverIneq * rho_used;
 #pragma unroll
     for (int t = 0; t < 3; t++) {
@@ -1113,31 +1134,60 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
   bool same_rho_resume = resumed && (rho == rho_used);
   // values only the factorisation, the termination check and the exit read: parked in accumulation registers, so that
   // they do not compete with the loop's own values for the architectural ones
-  AccD pEd[3], pEs[3], pEc[5], pIDx[3], pIDf[3], pUD0[3], pWX[3], pCs;
+  AccD pEd[3], pEs[3], pEc[5], pIDx[3], pIDf[3], pUD0[3], pCs;
+  // three figures of the last check that are read again only behind the loop (an exit always follows a check that computed
+  // all of them): parked too.  (The state weights wX used to be parked here; they are a function of the lane and are formed
+  // again where they are read.  Which of the check's figures are parked, which are scalars -- rho, pri_res -- is what the
+  // register allocation of the N = 16 kernels was found to fit with: docs/HISTORY.md 6b.)
+  AccD pNp, pDua, pNd;
+  pNp.set(0.0); pDua.set(0.0); pNd.set(0.0);
 #pragma unroll
   for (int t = 0; t < 3; t++) {
-    pEd[t].set(Ed[t]); pEs[t].set(Es[t]); pIDx[t].set(iDx[t]); pIDf[t].set(iDf[t]); pUD0[t].set(uD0[t]); pWX[t].set(wX[t]);
+    pEd[t].set(Ed[t]); pEs[t].set(Es[t]); pIDx[t].set(iDx[t]); pIDf[t].set(iDf[t]); pUD0[t].set(uD0[t]);
   }
 #pragma unroll
   for (int c = 0; c < 5; c++) pEc[c].set(Ec[c]);
   pCs.set(cs);
-#define QRW_UNPARK()                                                                                        \
+#define QRW_UNPARK()                                                                                         \
   double Ed[3], Es[3], Ec[5], iDx[3], iDf[3], uD0[3], wX[3];                                                \
   _Pragma("unroll") for (int t = 0; t < 3; t++) {                                                           \
     Ed[t] = pEd[t].get(); Es[t] = pEs[t].get(); iDx[t] = pIDx[t].get(); iDf[t] = pIDf[t].get();              \
-    uD0[t] = pUD0[t].get(); wX[t] = pWX[t].get();                                                           \
+    uD0[t] = pUD0[t].get();                                                                                   \
   }                                                                                                         \
   _Pragma("unroll") for (int c = 0; c < 5; c++) Ec[c] = pEc[c].get();                                       \
-  const double cs = pCs.get();
+  const double cs = pCs.get();                                                                              \
+  _Pragma("unroll") for (int t = 0; t < 3; t++)                                                             \
+    wX[t] = (j == 0) ? w_all[t] : (j == 1) ? w_all[3 + t] : (j == 2) ? w_all[6 + t] : w_all[9 + t];
+  // zeta_u = Omega_D u of the current factorisation, recomputed from rho_used where a block outside the plain iterations reads it
+  // (the same three roundings as when it was formed; the empty asm keeps it a rounded product, never half of a contracted fma)
+#define QRW_ZETA_U()                                                                                        \
+  double zeU[3];                                                                                            \
+  _Pragma("unroll") for (int t = 0; t < 3; t++) {                                                           \
+    zeU[t] = ((kRhoEqOverIneq * rho_used) * Ed[t] * Ed[t]) * uD0[t];                                        \
+    asm volatile("" : "+v"(zeU[t]));                                                                        \
+  }
 
   PH(8);
   // (PRE: from here on it_resume is the iteration this workgroup's CURRENT time slice began at -- it moves when a slice ends
   // without a taker being granted and the solve goes on in place; no second variable: the N = 32 kernels have no scalar to spare)
-  for (iter = it_resume + 1; iter <= max_iter; iter++) {
+  // The loop runs in check intervals: one outer round is [factorisation, if asked for] + kCheckEvery plain iterations + the
+  // check on the interval's last iterate.  The plain iterations hold no test of any kind.  What makes that exact:
+  //   - max_iter (4000) is a multiple of kCheckEvery (25), so the last interval is a full one and ends on max_iter;
+  //   - a factorisation is only ever asked for by a check (the adaptive-rho test) or on entry, so it falls on an interval
+  //     boundary;
+  //   - a resumed time slice (PRE) starts behind iteration it_resume, a multiple of 200 (the park follows the adaptive-rho
+  //     test, and mpc_preemptive_launch refuses a pre_chunk that is no multiple of 200), so resumes are interval-aligned.
+  // `iter` counts the iterations done; at every check it is the number of the iterate being checked, as it always was.
+  // Every decision that leaves or redirects the loop is the same in all lanes and is made a scalar (uniform_flag).
+  constexpr int kCheckEvery = 25;
+  static_assert(max_iter % kCheckEvery == 0 && 200 % kCheckEvery == 0, "checks, rho tests and max_iter fall on interval ends");
+  iter = it_resume;
+  for (;;) {
     PH(9);
     if (need_factor) {
       need_factor = false;
       QRW_UNPARK()
+      QRW_ZETA_U()
       const double rho_eq = kRhoEqOverIneq * rho;
       double omD[3], omS[3], omC[5];
 #pragma unroll
@@ -1152,7 +1202,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
           if constexpr (PRE) shift = same_rho_resume ? 0.0 : shift;
           thD[t] -= shift;
           wD[t] = act ? wD[t] + shift : 0.0;
-          zeU[t] = zu_new;
           aOD[t] = (j >= 2) ? 0.0 : alpha * omD[t];  // velocity rows take alpha dK instead (see the update)
           kD[t] = alpha * zu_new;
           aOS[t] = alpha * omS[t] * sfl[t];
@@ -1205,6 +1254,8 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
     PH(0);
     }  // need_factor
 
+#pragma nounroll
+    for (int plain = 0; plain < kCheckEvery; plain++) {
     // ---- 1. hatted right-hand side r = sigma x / D + A' E (rho z - y)      (OSQP compute_rhs + KKT reduction)
     double wC[5];
 #pragma unroll
@@ -1344,11 +1395,12 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
     }
 
     PH(6);
-    // ---- 5. termination / adaptive rho (OSQP update_info, check_termination, adapt_rho)
-    const bool check = (iter % 25 == 0);
-    if (check) {
-      PH(6);  // (diagnostic builds) everything up to here is the update phase; the check itself is accounted to slot 7
+    }  // plain iterations of this interval
+    iter += kCheckEvery;
+    // ---- 5. termination / adaptive rho (OSQP update_info, check_termination, adapt_rho) on the interval's last iterate
+    {
       QRW_UNPARK()
+      QRW_ZETA_U()
       const double cinv = fast_rcp(cs);
       // inverse scalings are only needed here (every 25 iterations): recomputed instead of held in registers
       double Dx[3], Df[3], iEd[3], iEs[3], iEc[5];
@@ -1407,17 +1459,19 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
       if (!act) { pres = nz = nax = 0.0; pres_s = nz_s = nax_s = 0.0; }
       pres = block_max<NW>(pres, L.sRed, wv, lane); nz = block_max<NW>(nz, L.sRed, wv, lane);
       nax = block_max<NW>(nax, L.sRed, wv, lane);
-      pri_res = pres;
+      pri_res = uniform_double(pres);
 #ifdef QRW_TRACE_RES
       if (tid == 0 && a.prof) a.prof[(size_t)b * kMpcProfItems + 64 + (iter / 25 - 1)] = pres / (eps_abs + eps_rel * fmax(nz, nax));
 #endif
       last_np = fmax(nz, nax);
+      pNp.set(last_np);
       const bool pri_ok = pri_res < eps_abs + eps_rel * last_np;
       // The dual residual is only needed to terminate (primal side passed), for the rho adaptation every 200
       // iterations and for the final approximate test at max_iter: skipped otherwise (never observable then).
-      const bool need_dual = pri_ok || (iter % 200 == 0) || (iter == max_iter) || (pri_res > kOsqpInfty);
+      const bool need_dual = uniform_flag(pri_ok || pri_res > kOsqpInfty) || (iter % 200 == 0) || (iter == max_iter);
       // dual side: D^-1 (P_s x + A_s' y) = c P xh + A' (E y)
       double dres = 0.0, naty = 0.0, npx = 0.0, dres_s = 0.0, naty_s = 0.0, npx_s = 0.0;
+      dua_res = last_nd = 0.0;  // (only ever read behind a check that computed them: no value is carried round the loop)
       if (need_dual) {
         double eD[3], eS[3], eC[5], cT[3];
 #pragma unroll
@@ -1455,20 +1509,20 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
         npx = block_max<NW>(npx, L.sRed, wv, lane);
         dua_res = cinv * dres;
         last_nd = cinv * fmax(naty, npx);
+        pDua.set(dua_res); pNd.set(last_nd);
       }
-      bool done = false;
       if (need_dual) {
-        if (pri_res > kOsqpInfty || dua_res > kOsqpInfty) {
+        if (uniform_flag(pri_res > kOsqpInfty || dua_res > kOsqpInfty)) {
           status = kStatusNonCvx;
-          done = true;
-        } else if (pri_ok && dua_res < eps_abs + eps_rel * last_nd) {
+          break;
+        }
+        if (uniform_flag(pri_ok && dua_res < eps_abs + eps_rel * last_nd)) {
           // is_primal_infeasible / is_dual_infeasible can never fire for this QP: the cone rows have
           // l = -inf (their u'dy+ + l'dy- sum is NaN in OSQP's arithmetic) and q = 0 (q'dx = 0).
           status = kStatusSolved;
-          done = true;
+          break;
         }
       }
-      if (done) break;
       if (iter % 200 == 0) {  // adapt_rho on the SCALED residuals (compute_rho_estimate)
         pres_s = block_max<NW>(pres_s, L.sRed, wv, lane); nz_s = block_max<NW>(nz_s, L.sRed, wv, lane);
         nax_s = block_max<NW>(nax_s, L.sRed, wv, lane); dres_s = block_max<NW>(dres_s, L.sRed, wv, lane);
@@ -1477,8 +1531,8 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
         const double dn = dres_s / (fmax(naty_s, npx_s) + 1e-10);
         double rho_new = rho * sqrt(pn / (dn + 1e-10));
         rho_new = fmin(fmax(rho_new, kRhoMin), kRhoMax);
-        if (rho_new > rho * 5.0 || rho_new < rho / 5.0) {
-          rho = rho_new;  // osqp_update_rho: clip, refresh rho_vec, refactor
+        if (uniform_flag(rho_new > rho * 5.0 || rho_new < rho / 5.0)) {
+          rho = uniform_double(rho_new);  // osqp_update_rho: clip, refresh rho_vec, refactor
           rho_updates++;
           need_factor = true;
         }
@@ -1491,7 +1545,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
         if constexpr (PRE) {  // end of this workgroup's time slice (after the rho test, before iteration iter + 1): park the solve
           // here if a taker workgroup is granted for it, go on with the next slice in place otherwise (pre_next_task above)
           if (iter - it_resume >= a.pre_chunk && iter < max_iter) {
-            if (pre_may_park<NW>(a, &L.sBal[0], tid)) parked = true;
+            if (uniform_flag(pre_may_park<NW>(a, &L.sBal[0], tid))) parked = true;
             else it_resume = iter;
           }
           if (tid == 0) {  // how far from termination (the queue's priority level is predicted from two consecutive tests, at the park)
@@ -1505,12 +1559,14 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
         if (parked) break;
       }
     }
+    if (iter >= max_iter) break;  // (status stays kStatusUnsolved: the 10x re-check below)
   }
   PH(7);
 #ifdef QRW_PROFILE_PHASES
   if (tid == 0 && a.prof) for (int i = 0; i < 10; i++) a.prof[(size_t)b * kMpcProfItems + i] = (double)ph_acc[i];
 #endif
   if (iter > max_iter) iter = max_iter;
+  last_np = pNp.get(); dua_res = pDua.get(); last_nd = pNd.get();
   if (status == kStatusUnsolved && !parked) {
     // max_iter reached (4000 % 25 == 0: the residuals of the last iterate were just computed): OSQP re-checks with
     // 10x tolerances, check_termination(work, 1)
@@ -1521,7 +1577,13 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
 
   // =========================== E. results + persistent state ===========================
   {
+  // (the thread's indices, derived again from a copy of the thread index that the compiler cannot trace: the element offsets
+  // of the stores below are then computed here instead of being carried from the set-up through the whole ADMM loop)
+  int tid_e = threadIdx.x;
+  asm volatile("" : "+v"(tid_e));
+  const int tid = tid_e, k = 16 * ((NW == 1) ? 0 : tid_e >> 6) + ((tid_e & 63) >> 2), j = tid_e & 3;
   QRW_UNPARK()
+  QRW_ZETA_U()
   const bool has_sol = (status != kStatusNonCvx);
   if (act && !parked) {
 #pragma unroll
@@ -1603,6 +1665,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mpc_solve_kernel(MpcArgs a) {
   }
   }
 #undef QRW_UNPARK
+#undef QRW_ZETA_U
 #undef ST
 }
 
@@ -1701,7 +1764,7 @@ int mpc_order_launch(const int* iters, float* ema, int* order, int B, hipStream_
 
 // preemptive launch (N > 16 only): B * pre_cmax workgroups, the caller has reset pre_queue (-1) and pre_ctr (0) on the stream
 int mpc_preemptive_launch(const MpcArgs& a_in, int resident_slots, hipStream_t stream) {
-  if (a_in.N <= 16 || a_in.N > kMpcMaxN || !a_in.pre_queue || !a_in.pre_ctr || !a_in.pause_it || a_in.pre_chunk < 200 || a_in.pre_cmax < 1 ||
+  if (a_in.N <= 16 || a_in.N > kMpcMaxN || !a_in.pre_queue || !a_in.pre_ctr || !a_in.pause_it || a_in.pre_chunk < 200 || a_in.pre_chunk % 200 != 0 || a_in.pre_cmax < 1 ||  // (slices end at adaptive-rho tests: the ADMM loop's resume is interval-aligned)
       a_in.pre_levels < 1 || a_in.pre_levels > kPreMaxLevels || a_in.pre_bin < 1) return -1;
   MpcArgs a = a_in;
   auto go = [&](unsigned blocks) {

@@ -9,8 +9,9 @@ wrong results (docs/HISTORY.md 6b) had run out of AGPRs and spilled to scratch w
 mpc_solve_kernel instantiation:
   (a) no scratch_ instruction anywhere in the kernel;
   (b) every AGPR an asm block reads is written by some asm block of the kernel;
-  (c) listings built with -DQRW_MARK_PHASES only: on the hot path of an ADMM iteration (phase markers 0 .. 6: right-hand
-      side, force elimination, sweeps, Delta^-1 products, updates) no compiler-generated instruction writes an AGPR that an
+  (c) listings built with -DQRW_MARK_PHASES only: on the hot path of an ADMM iteration (from phase marker 0 through the markers
+      of phases 1 .. 6, in whatever order the loop of plain iterations is laid out: right-hand side, force elimination,
+      sweeps, Delta^-1 products, updates) no compiler-generated instruction writes an AGPR that an
       asm block of that region reads, i.e. the Delta^-1 rows sit untouched in their registers from one factorisation to the
       next, and no scratch access happens there.
 What this does and does not show: every build that has passed the GPU parity tests satisfies (a)-(c); the wrong build of
@@ -87,7 +88,14 @@ def scan(name, lines):
     if marks:
         p0 = [i for i, p in marks if p == 0]
         lo = p0[0] if p0 else None
-        hi = next((i for i, p in marks if p == 6 and lo is not None and i > lo), None)
+        # the plain iterations are a loop of their own behind the factor block, and the compiler is free to lay that loop out
+        # rotated (e.g. markers 0, 5, 6, 1, 2, 3, 4): the hot path runs from marker 0 to the last marker of phases 1 .. 6 ahead of
+        # the check block (marker 7), and on to the branch that closes the loop
+        end = next((i for i, p in marks if p == 7 and lo is not None and i > lo), len(lines))
+        body = [i for i, p in marks if 1 <= p <= 6 and lo is not None and lo < i < end]
+        hi = body[-1] if body and any(p == 6 for i, p in marks if i in body) else None
+        if hi is not None:
+            hi = next((i for i in range(hi, end) if lines[i].strip().startswith(("s_branch", "s_cbranch_scc"))), hi)
         if lo is None or hi is None:
             findings.append("%s: phase markers 0 / 6 not found in order" % name)
         else:
